@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- MPC-QP solves/sec (horizon-10 SRBD) of the MI355X engine, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path (QP formation + OSQP-faithful ADMM solve, cold start) over one batch of
 synthetic input: BASELINE.json configs[2] -- 4096 randomized CoM states, flat terrain, horizon 10, per GPU
 (weak scaling: every rank gets its own 4096 QPs, generated from a rank-specific seed; the batch is
 embarrassingly parallel, so there is no data-path collective).  Inputs are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+region.  Rank 0 prints ONE JSON line: `value` (solves/s) and `ms_per_step` of exactly K timed steps.  A plain run measures nothing
+else; --full adds everything measured beside `value` (single-stream and index-order steps, stage counters, `roofline`, latency probes,
+other shapes, `cpu_baseline`, parity against the oracle).  --dump-outputs DIR writes the last timed step's outputs as .npy files.
 """
 import argparse
 import json
@@ -26,6 +28,23 @@ PMC_SUMMARY = "r06_pmc_summary.json"   # static rocprofv3 --pmc summary of this 
 FP64_PEAK_TFLOPS = 78.6  # MI355X FP64 vector = matrix peak (AMD spec; = 1/2 of the 157.3 TF FP32 rate in MI355X_MICROARCH.md)
 BATCH = 4096
 HORIZON = 10
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path returned to its caller in its last step, one DIR/<name>.npy each, as float64 (iteration counts and statuses
+    are exact in it).  All arrays share their first axis (one row per QP); beyond DUMP_LIMIT_BYTES a fixed, seeded sample of rows is written, with its row
+    indices as sample_rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    row_bytes = sum(a[:1].nbytes for a in arrays.values()) + 8
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def single_thread_ticks(pkg, oracle, pr, horizon, nticks=10000, budget_s=8.0):
@@ -630,6 +649,8 @@ def strong_scaling_config4(pkg, args, rank, world, local, backend, dist):
     part = participation(dist, rank, world, local, backend)   # (a collective: every rank calls it)
     if rank == 0:
         iters = out_bufs[1][:, 0].cpu().numpy(); status = out_bufs[1][:, 1].cpu().numpy()
+        if args.dump_outputs:   # what the last timed step gathered on rank 0
+            dump_outputs(args.dump_outputs, {"grf": out_bufs[0].cpu().numpy(), "iters": iters, "status": status})
         res = {"metric": "MPC QP solves/sec (horizon=16 SRBD), BASELINE configs[3]", "value": N * args.steps / elapsed, "unit": "solves/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
                "dtype": "f64", "data": "synthetic",
@@ -647,6 +668,28 @@ def strong_scaling_config4(pkg, args, rank, world, local, backend, dist):
             res["config"]["parallelism"] += f" -- {part['distinct_devices']} distinct GPU(s) for {world} rank(s): NOT a scaling point"
     eng.close()
     return res
+
+
+def metric_line(n, world, args, elapsed, depth, untimed, it, stt, part, backend):
+    """the line of BASELINE configs[2]'s metric (everything a plain run prints): `value`, `ms_per_step`, the workload and who took part; `it` / `stt` are the
+    iterations and statuses of batch 0"""
+    import torch
+    out = {
+        "metric": "MPC QP solves/sec (horizon=10 SRBD)", "value": world * n * args.steps / elapsed, "unit": "solves/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]: batch=4096 randomized CoM states + flat terrain, horizon=10, cold-start "
+                               "OSQP-default ADMM, per GPU; 4 distinct batches cycled, every step a first solve (no queue-order history); "
+                               f"{depth} batch(es) in flight (a1mpc_pipeline: one engine handle + HIP stream per slot, round-robin)",
+                   "batch_per_gpu": n, "horizon": HORIZON, "parallelism": f"batch-sharded x{world}" + (f" ({backend}, ranks SHARING {torch.cuda.device_count()} physical GPU(s): a smoke "
+                                                                                                   "test of the N > 1 path, not a scaling point)" if os.environ.get("A1_BENCH_SHARE_GPU") else ""),
+                   "batches_in_flight": depth, "untimed_launches_before_timing": untimed,
+                   "mean_iters": float(it.mean()), "max_iters": int(it.max()), "solved_frac": float((stt == 1).mean())},
+    }
+    out["config"].update(part)   # who took part: distinct_devices, rccl_world_size, is_scaling_point, device_ids (flat scalars of `config`)
+    if not part["is_scaling_point"]:
+        out["config"]["parallelism"] += f" -- {part['distinct_devices']} distinct GPU(s) for {world} rank(s): NOT a scaling point"
+    return out
 
 
 def spawn_ranks(args):
@@ -685,7 +728,7 @@ def native_sharded(args):
     NB = 2 if cfg4 else 4
     scs = [gen(nb=n, seed=0xA1 + 3 + 17 * k) for k in range(NB)]
     cfg = pkg.make_config(scs[0]["params"], h, warm_start=0)
-    res = {}
+    res, last = {}, {}
     for transport in (0, 1):
         devs = [g % have for g in range(args.gpus)] if transport == 0 else list(range(min(args.gpus, have)))
         try:
@@ -696,6 +739,7 @@ def native_sharded(args):
                 for k in range(args.steps):
                     s = scs[k % NB]; o = sh.solve(s["x0"], s["xref"], s["R"], s["foot"], s["contact"])
                 el = time.perf_counter() - t0
+                last[transport] = o
                 res[transport] = {"transport": "pinned fan-out, one hipMemcpyAsync per device each way" if transport == 0 else "RCCL grouped ncclSend / ncclRecv through shard 0's GPU",
                                   "devices": devs, "solves_per_s": n * args.steps / el, "ms_per_step": el / args.steps * 1e3, "mean_iters": float(o["iters"].mean()),
                                   "solved_frac": float((o["status"] == 1).mean())}
@@ -704,6 +748,9 @@ def native_sharded(args):
     pick = res[args.native]
     if "error" in pick:
         raise SystemExit(f"--native {args.native}: {pick['error']}")
+    if args.dump_outputs:   # the chosen transport's last timed step
+        o = last[args.native]
+        dump_outputs(args.dump_outputs, {"grf": o["grf"], "iters": o["iters"], "status": o["status"]})
     out = {"metric": f"MPC QP solves/sec (horizon={h} SRBD), host arrays in / out through a1mpc_sharded_* (PCIe inclusive)", "value": pick["solves_per_s"], "unit": "solves/s",
            "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": pick["ms_per_step"], "higher_is_better": True, "scaling": "strong" if cfg4 else "weak",
            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -724,12 +771,19 @@ def main():
                     "4: BASELINE configs[3], 65536 x h16 in total, sharded over the GPUs with scatter + gather inside the timed region (strong scaling)")
     ap.add_argument("--depth", type=int, default=2, help="batches in flight (a1mpc_pipeline: one engine handle + HIP stream each, submitted round-robin); "
                     "1 = one handle, launches serialised on one stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-index-order", action="store_true", help="skip the extra index-order steps (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside `value` as well: single-stream and index / history-order steps, stage counters, "
+                    "roofline, latency probes, other shapes and horizons, CPU baseline and parity against the oracle.  Without it the run sets up, warms up, "
+                    "times the steps and prints the metric's line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float64; the inputs are seeded, so two builds can be compared output for output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline and the parity block")
+    ap.add_argument("--no-latency", action="store_true", help="(with --full) skip the latency probes, sweeps and other shapes")
+    ap.add_argument("--no-index-order", action="store_true", help="(with --full) skip the extra index-order steps (profiling runs)")
     ap.add_argument("--native", type=int, default=-1, choices=(-1, 0, 1), help="one process, all --gpus GPUs through the C ABI's own sharding (a1mpc_sharded_*, host arrays in / out): "
                     "0 = pinned fan-out (one hipMemcpyAsync per device each way), 1 = RCCL grouped send / recv through shard 0's GPU; both are measured, the chosen one is `value`")
     args = ap.parse_args()
+    if not args.full:   # a plain run measures `value` and nothing else
+        args.no_cpu_baseline = args.no_latency = args.no_index_order = True
 
     import torch
     if not torch.cuda.is_available():
@@ -783,7 +837,8 @@ def main():
     outs = [(torch.zeros((n, 12), dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
             for _ in range(NB)]           # one output set per resident batch: a batch in flight never shares its outputs with the next one
     depth = max(1, min(args.depth, NB))
-    eng = pkg.Engine(cfg, n, local)       # the lone handle: single-stream figures, index / history order, work collection
+    eng = pkg.Engine(cfg, n, local)       # the lone handle: single-stream figures, index / history order, work collection (--full; created in a plain run too,
+                                          #  so that the timed pipeline is set up exactly as in a --full run)
     pipe = pkg.Pipeline(cfg, n, local, depth=depth)   # `value`: `depth` batches in flight, the next batch fills the tail of the one before
     stream = torch.cuda.Stream(device=dev)  # a real (non-null) HIP stream: kernels and the timing events share it
     torch.cuda.synchronize()
@@ -831,10 +886,13 @@ def main():
     elapsed = time.perf_counter() - t0
     pipe_ms = e0.elapsed_time(e1) / args.steps   # device time per batch with `depth` batches in flight
     pipe_out0 = tuple(t_.cpu().numpy().copy() for t_ in outs[0])   # what the timed region left for batch 0 (GRFs, iterations, status): the parity block checks THESE
+    if args.dump_outputs and rank == 0:   # the batch of the last timed step, before anything below launches again
+        last = outs[(args.steps - 1) % NB]
+        dump_outputs(args.dump_outputs, {"grf": last[0].cpu().numpy(), "iters": last[1].cpu().numpy(), "status": last[2].cpu().numpy()})
     # continuity with the round-3 protocol (ADVICE r4 / VERDICT r4 item 7): the same K steps behind only 8 untimed launches, the GPU idle for a second before them
     # (round 3 timed exactly that; round 4 moved to 32 untimed launches, which is worth ~5 % through the clocks alone).  Reported beside `value`, never instead of it.
     value8 = None
-    if world == 1 and os.environ.get("A1_BENCH_VALUE8", "1") != "0":
+    if args.full and world == 1 and os.environ.get("A1_BENCH_VALUE8", "1") != "0":
         time.sleep(1.0)
         region(8); pipe.wait(); torch.cuda.synchronize()
         t8 = time.perf_counter(); region(args.steps); torch.cuda.synchronize()
@@ -843,6 +901,15 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if not args.full:
+        part = participation(dist, rank, world, local, backend)   # (a collective: every rank calls it)
+        if rank == 0:
+            print(json.dumps(metric_line(n, world, args, elapsed, depth, spin_up + args.warmup, pipe_out0[1], pipe_out0[2], part, backend)), flush=True)
+        eng.close(); pipe.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the same steps through the lone handle on one stream (launches serialised): per-launch durations by HIP events, what a kernel trace shows
     for k in range(2):
@@ -906,17 +973,8 @@ def main():
         except Exception:
             pass
         traffic = float(pmc["hbm_bytes_per_launch"]) if (n == BATCH and "hbm_bytes_per_launch" in pmc) else None
-        out = {
-            "metric": "MPC QP solves/sec (horizon=10 SRBD)", "value": world * n * args.steps / elapsed, "unit": "solves/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: batch=4096 randomized CoM states + flat terrain, horizon=10, cold-start "
-                                   "OSQP-default ADMM, per GPU; 4 distinct batches cycled, every step a first solve (no queue-order history); "
-                                   f"{depth} batch(es) in flight (a1mpc_pipeline: one engine handle + HIP stream per slot, round-robin)",
-                       "batch_per_gpu": n, "horizon": h, "parallelism": f"batch-sharded x{world}" + (f" ({backend}, ranks SHARING {torch.cuda.device_count()} physical GPU(s): a smoke "
-                                                                                                 "test of the N > 1 path, not a scaling point)" if os.environ.get("A1_BENCH_SHARE_GPU") else ""),
-                       "batches_in_flight": depth, "untimed_launches_before_timing": spin_up + args.warmup,
-                       "mean_iters": float(it.mean()), "max_iters": int(it.max()), "solved_frac": float((stt == 1).mean())},
+        out = metric_line(n, world, args, elapsed, depth, spin_up + args.warmup, it, stt, part, backend)
+        out.update({
             "roofline": {"bound": "fp64-valu", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic,
                          "traffic_source": f"static: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, profiles/{PMC_SUMMARY}" if traffic else None,
@@ -936,10 +994,7 @@ def main():
                                  "on MI355X).  TWO fractions, always side by side: `frac` prices the SURVEY 8(d) dense-condensed flop model F(h,iters,nfact) (what a dense solver "
                                  "would execute; the structured Riccati solve executes 1.5x / 2.8x / 3.9x fewer flops at h = 10 / 16 / 20), `executed_fp64_frac` prices the FP64 flops "
                                  "the kernels really issue (SQ_INSTS_VALU_{FMA,ADD,MUL}_F64 x live lanes from the static PMC profile) -- the hardware fraction"},
-        }
-        out["config"].update(part)   # who took part: distinct_devices, rccl_world_size, is_scaling_point, device_ids (flat: the driver's record keeps them)
-        if not part["is_scaling_point"]:
-            out["config"]["parallelism"] += f" -- {part['distinct_devices']} distinct GPU(s) for {world} rank(s): NOT a scaling point"
+        })
         out["stage_counters"] = stage
         # ---- scalars a reader of this line needs first; repeated inside `roofline` and `config`, which the driver keeps whole
         admm_ms = stage.get("solve_ms") if isinstance(stage, dict) else None   # the persistent ADMM kernel (+ the ~6 us order kernel) of one launch alone, by HIP events

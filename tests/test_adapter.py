@@ -1,6 +1,6 @@
 """The C++ side of the boundary: include/a1mpc_dropin.hpp (the reference's ConvexMpc / compute_grf interface over the C ABI) and the C++
-latency harness.  The programs are built by tests/cpp/Makefile -- the two that include the reference's headers only where /root/reference
-exists (this container); the binaries travel to the GPU box with the snapshot."""
+latency harness.  The programs are built by tests/cpp/Makefile -- the two that include the reference's sources by oracle/Makefile `dropin`,
+into oracle/_ref/ beside the reference libraries, where the reference's tree exists; they travel with oracle/_ref/."""
 import json
 import os
 import subprocess
@@ -9,6 +9,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CPP = os.path.join(ROOT, "tests", "cpp")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
 
 
 def _build(pkg):
@@ -22,15 +23,17 @@ def test_dropin_programs_compile_and_link(pkg):
     """a1mpc_dropin.hpp instantiated on the reference's A1CtrlStates next to the reference's own A1RobotControl (test_dropin), the reference's
     S/test/test_mpc.cpp compiled UNMODIFIED against the drop-in ConvexMpc (test_mpc_dropin), and the C-ABI latency harness."""
     _build(pkg)
-    have_ref = os.path.isdir("/root/reference/src/a1_cpp/src")
-    for exe in ("latency_harness",) + (("test_dropin", "test_mpc_dropin") if have_ref else ()):
-        assert os.path.exists(os.path.join(CPP, exe)), exe
+    import ref as REF
+    assert os.path.exists(os.path.join(CPP, "latency_harness"))
+    if os.path.isdir(REF.REFERENCE_SRC):
+        for exe in ("test_dropin", "test_mpc_dropin"):
+            assert os.path.exists(os.path.join(REF_BIN, exe)), exe
 
 
 def _run(exe, *args, timeout=300):
-    path = os.path.join(CPP, exe)
+    path = os.path.join(CPP if exe == "latency_harness" else REF_BIN, exe)
     if not os.path.exists(path):
-        pytest.skip(f"{exe} was not built (needs /root/reference at build time)")
+        pytest.skip(f"{exe} was not built (needs the reference's sources at build time)")
     return subprocess.run([path, *args], capture_output=True, text=True, timeout=timeout)
 
 

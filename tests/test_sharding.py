@@ -158,7 +158,7 @@ def _run_bench(*flags, timeout=420):
 def test_bench_gpus_2_spawns_its_own_ranks():
     """`python bench.py --gpus 2` with WORLD_SIZE unset starts two ranks itself and prints n_gpus = 2 -- on the one-GPU test box the two ranks
     share the GPU over gloo (said so in config.parallelism); both the weak-scaling metric and --config 4 (scatter + solve + gather in the timed region) run end to end."""
-    out = _run_bench("--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-latency", "--no-index-order")
+    out = _run_bench("--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-latency", "--no-index-order")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0 and out["config"]["solved_frac"] == 1.0
     assert "roofline" in out and out["unit"] == "solves/s"
     # round 6: the line proves which devices took part -- two ranks on ONE physical GPU are labelled, never counted as a scaling point

@@ -6,12 +6,12 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/$TAG; mkdir -p $O
 timeout 100 python -c "import torch"
 [ -z "$SKIP_COLLECT" ] && timeout 1500 bash tools/collect_profiles.sh $TAG > $O/collect.log 2>&1
 [ -z "$SKIP_COLLECT" ] && python tools/summarize_profiles.py $TAG > $O/summarize.log 2>&1   # the bench line's roofline.traffic / executed-FP64 figures are read from this run's PMC summary
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err   # (the driver's command line)
-timeout 300 python bench.py --depth 1 --no-cpu-baseline --no-latency > $O/bench_depth1.json 2> /dev/null
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err   # (the metric's command line + everything measured beside it)
+timeout 300 python bench.py --depth 1 --full --no-cpu-baseline --no-latency > $O/bench_depth1.json 2> /dev/null
 timeout 100 tests/cpp/latency_harness 10000 > $O/latency_10000.json 2>/dev/null
 timeout 100 tests/cpp/latency_harness 4000 2000 > $O/latency_paced.json 2>/dev/null
 timeout 200 python bench.py --config 4 --steps 5 --warmup 2 > $O/bench_config4_n1.json 2>/dev/null
-timeout 300 python bench.py --gpus 2 --steps 10 --warmup 4 --no-cpu-baseline --no-latency --no-index-order > $O/bench_gpus2_shared_gpu_gloo.json 2>/dev/null
+timeout 300 python bench.py --gpus 2 --steps 10 --warmup 4 --full --no-cpu-baseline --no-latency --no-index-order > $O/bench_gpus2_shared_gpu_gloo.json 2>/dev/null
 timeout 300 python bench.py --gpus 2 --config 4 --steps 3 --warmup 1 > $O/bench_config4_2ranks_shared_gpu_gloo.json 2>/dev/null
 timeout 300 python bench.py --native 0 --gpus 2 --steps 10 --warmup 4 > $O/bench_native_2shards_one_gpu.json 2>/dev/null
 timeout 200 python tools/pcie_probe.py 4096 10 60 > $O/pcie_probe_4096_h10.json 2>/dev/null

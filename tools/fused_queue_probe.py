@@ -44,7 +44,7 @@ for flag in ("0", "1", "0", "1"):
     res = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
     lines.append(f"A1MPC_FUSED_QUEUE={flag} one stream: " + (res[0][7:] if res else "FAILED " + r.stderr[-300:]))
     print(lines[-1], flush=True)
-    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-latency", "--no-cpu-baseline", "--no-index-order"], capture_output=True, text=True,
+    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-latency", "--no-cpu-baseline", "--no-index-order"], capture_output=True, text=True,
                        timeout=300, env=dict(env, A1_BENCH_VALUE8="0"))
     try:
         d = json.loads([l for l in b.stdout.splitlines() if l.startswith("{")][-1])
