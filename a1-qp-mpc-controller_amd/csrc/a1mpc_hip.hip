@@ -508,7 +508,6 @@ struct a1mpc_handle_s {
     double tick_km[3] = {0, 0, 0};
     bool staged = false;
     bool busy = false;
-    size_t zc_poll_bytes = 0;   // > 0: host_submit launched a kernel that writes its outputs into the pinned block itself and filled that many bytes of it with the in-flight pattern (a1mpc_solve_batch polls them)
     int pipeline_depth = 0;      // > 0: this handle is a slot of an a1mpc_pipeline with that many slots (g_gen_prefer_one_wave)
     // carried OSQP workspace (warm start)
     double *d_wx = nullptr, *d_wy = nullptr, *d_rho = nullptr;
@@ -537,10 +536,8 @@ struct a1mpc_handle_s {
     // packed device blocks + pinned host mirrors of the host-pointer MPC entry (one copy each way per call)
     char *d_in = nullptr, *d_out = nullptr;
     char* h_pin = nullptr;
-    char* d_pin = nullptr;   // the pinned block as the device sees it (hipHostGetDevicePointer), or null: small batches read / write it directly (host_submit)
+    char* d_pin = nullptr;   // the pinned block as the device sees it (hipHostGetDevicePointer), or null: small batches read / write it directly (pin_inputs)
     size_t h_pin_bytes = 0, h_pin_in_bytes = 0;
-    char *h_pin_gen = nullptr, *d_pin_gen = nullptr;   // a small pinned block for the general path's inputs of <= 8 QPs (per-step feet / contacts do not fit the block above), allocated on first use
-    size_t h_pin_gen_bytes = 0;
 };
 
 static a1mpc_status order_streams(a1mpc_handle h, hipStream_t s) {
@@ -1695,7 +1692,6 @@ void a1mpc_destroy(a1mpc_handle h) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
-    if (h->h_pin_gen) (void)hipHostFree(h->h_pin_gen);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_order) (void)hipEventDestroy(h->ev_order);
@@ -1706,6 +1702,15 @@ void a1mpc_destroy(a1mpc_handle h) {
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
+
+// The small-batch path of the host-pointer entries (pin_inputs): batches of up to A1MPC_ZERO_COPY_MAX QPs (default 8; 0 = always stage through device memory).
+// The general path takes it for at most 64 QPs, so that a large setting cannot inflate the pinned block a1mpc_create sizes for it.
+static int zero_copy_max() {
+    static const int m = [] { const char* e = getenv("A1MPC_ZERO_COPY_MAX"); return e ? atoi(e) : 8; }();
+    return m;
+}
+static size_t small_general_max() { return zero_copy_max() <= 64 ? static_cast<size_t>(std::max(zero_copy_max(), 0)) : 0; }
+static bool small_batch(a1mpc_handle h, int32_t n) { return n <= zero_copy_max() && h->d_pin != nullptr; }
 
 a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t device, a1mpc_handle* out) {
     if (!cfg || !out || max_batch <= 0 || device < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null config/out or bad batch/device");
@@ -1770,11 +1775,16 @@ a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t de
     A1_TRY(hipMalloc(&h->d_order, n * sizeof(int32_t)));
     A1_TRY(hipMalloc(&h->d_cost, n * sizeof(int32_t)));
     if (const char* e = std::getenv("A1MPC_SCHEDULE")) h->schedule = std::strcmp(e, "index") != 0;
-    // pinned mirror: inputs (x0, xref, R, Rz, foot, aux, contact) then outputs (grf, u, iters, status)
-    h->h_pin_in_bytes = n * ((13 + 13 * H + 9 + 12) * sizeof(double) + 8);
+    // pinned block: the input region, which holds every small-batch layout for every n the small path takes (pin_inputs), then the output region
+    // [grf | iters | status | u] (host_out_layout).  Per QP: the fast layout -- x0, x_ref, R, feet, contacts; the tick-record and balance layouts are smaller -- for
+    // up to max_batch QPs (it is also what a staged launch copies into d_in), the general layout -- x0, x_ref, R, 12H feet, yaw, 4H contacts -- for up to
+    // small_general_max() QPs.
+    const size_t fast_in = n * ((13 + 13 * H + 9 + 12) * sizeof(double) + 8);
+    const size_t gen_in = std::min(n, small_general_max()) * ((13 + 13 * H + 9 + 12 * H + 1) * sizeof(double) + (4 * H + 7) / 8 * 8);
+    h->h_pin_in_bytes = std::max(fast_in, gen_in);
     const size_t out_max = n * ((12 + 12 * H) * sizeof(double) + 2 * sizeof(int32_t));
     h->h_pin_bytes = h->h_pin_in_bytes + out_max;
-    A1_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_in), h->h_pin_in_bytes));
+    A1_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_in), fast_in));
     A1_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_out), out_max));
     A1_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_pin), h->h_pin_bytes, hipHostMallocDefault));
     { void* dp = nullptr; if (hipHostGetDevicePointer(&dp, h->h_pin, 0) == hipSuccess) h->d_pin = static_cast<char*>(dp); else (void)hipGetLastError(); }
@@ -2276,8 +2286,95 @@ a1mpc_status a1mpc_last_control_tick_ms(a1mpc_handle h, float* ms_out, int32_t* 
     return A1MPC_OK;
 }
 
-static a1mpc_status ticks_small_batch(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs, const uint8_t* contact, double* grf_body_out,
-                                      double* u_full_out, int32_t* iters_out, int32_t* status_out, bool* taken);
+// ---- the small-batch transport of the host-pointer entries.  A handful of QPs (the drop-in's calls are n = 1) is not staged through device memory: the caller's
+// arrays are packed into the handle's PINNED block (device-mapped host memory: 1.3 KB in, ~100 B out per QP over PCIe, a few transactions), the kernel reads its
+// inputs from and writes its results to that block itself, and the host polls the output words -- the staging copies each cost more on the GPU's timeline than
+// the bytes they move.  Same kernels, same bits.  Each entry states its layout and its launch: pin_inputs, arm_outputs, launch, wait_outputs, host_collect.
+//
+// Every output word is its own completion flag.  The bytes the kernel is about to write are filled with a bit pattern no result has (a quiet NaN with a payload as a
+// double -- forces are finite or exactly zero, a failed solve's u is the payload-free NaN --, 0x7ff85a5a as an int32: no iteration count, no status), and the host
+// polls until no word holds it any more instead of waiting in hipStreamSynchronize(): it is awake 5 us earlier (p99: 9 us; tools/ubench/completion_wake_ubench.hip).
+// No ordering between the kernel's stores is assumed: polling `status` alone, stored last behind a system-scope release, saw the forces arrive AFTER it on 2 of
+// 10 000 ticks (posted writes over PCIe with relaxed ordering).
+constexpr unsigned long long kInFlightWord = 0x7ff85a5a7ff85a5aull;
+
+// The output region of N QPs from `base` (the pinned block's, as the host or the device sees it, or d_out for a staged launch): [grf | iters | status | u], u_width
+// doubles of u per QP -- 12H for the MPC entries, 12 (f_world) for the balance QP, 0 where the caller passed no such array (u = null).  bytes: what a launch writes.
+struct HostOut { double* grf; int32_t *iters, *status; double* u; size_t bytes; };
+static HostOut host_out_layout(char* base, size_t N, size_t u_width) {
+    const size_t q_it = N * 12 * sizeof(double), q_st = q_it + N * sizeof(int32_t), q_u = q_st + N * sizeof(int32_t);
+    return {reinterpret_cast<double*>(base), reinterpret_cast<int32_t*>(base + q_it), reinterpret_cast<int32_t*>(base + q_st),
+            u_width ? reinterpret_cast<double*>(base + q_u) : nullptr, q_u + N * u_width * sizeof(double)};
+}
+
+// The caller's arrays packed, in the order given, into the pinned block's input region (the double arrays first, the byte arrays last, each at an 8-byte aligned
+// offset; a null array takes no room and has a null address).  f64(i), u8(i): array i as the device sees it from `base` -- d_pin, or d_in after a staged copy of `bytes`.
+struct PinIn { const void* src; size_t bytes; };
+struct PinnedIn {
+    static constexpr size_t kNone = ~size_t(0);
+    const char* base; size_t off[6]; size_t bytes;   // (six arrays at most: the general path's layout)
+    const char* at(int i) const { return off[i] == kNone ? nullptr : base + off[i]; }
+    const double* f64(int i) const { return reinterpret_cast<const double*>(at(i)); }
+    const uint8_t* u8(int i) const { return reinterpret_cast<const uint8_t*>(at(i)); }
+};
+static PinnedIn pin_inputs(a1mpc_handle h, std::initializer_list<PinIn> arrays) {
+    PinnedIn p{h->d_pin, {}, 0};
+    int i = 0;
+    for (const PinIn& a : arrays) {
+        const size_t o = (p.bytes + 7) / 8 * 8;
+        p.off[i++] = a.src ? o : PinnedIn::kNone;
+        if (a.src) { std::memcpy(h->h_pin + o, a.src, a.bytes); p.bytes = o + a.bytes; }
+    }
+    return p;
+}
+
+// Arms the output region for a small-batch launch of N QPs (every word it will write holds kInFlightWord) and returns it as the device sees it
+static HostOut arm_outputs(a1mpc_handle h, size_t N, size_t u_width) {
+    const HostOut o = host_out_layout(h->d_pin + h->h_pin_in_bytes, N, u_width);
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(h->h_pin + h->h_pin_in_bytes);
+    for (size_t i = 0; i < o.bytes / 8; ++i) w[i] = kInFlightWord;
+    std::atomic_thread_fence(std::memory_order_release);
+    return o;
+}
+
+// Has the kernel written every armed word?  [12N grf doubles | 2N iters, status int32 | u doubles up to `armed` bytes]
+static bool outputs_landed(const char* hout, size_t N, size_t armed) {
+    const volatile unsigned long long* w64 = reinterpret_cast<const volatile unsigned long long*>(hout);
+    const volatile uint32_t* w32 = reinterpret_cast<const volatile uint32_t*>(hout);
+    for (size_t i = 24 * N; i < 26 * N; ++i) if (w32[i] == static_cast<uint32_t>(kInFlightWord)) return false;   // (written last by the kernel: the cheap test first)
+    for (size_t i = 0; i < 12 * N; ++i) if (w64[i] == kInFlightWord) return false;
+    for (size_t i = 13 * N; i < armed / 8; ++i) if (w64[i] == kInFlightWord) return false;
+    return true;
+}
+
+// Waits for the launch just queued on the handle's stream: polls the `armed` bytes of the output region (and the stream now and then: a launch that failed never
+// writes them), or synchronises the stream where nothing was armed (a staged launch).  A word still in flight once the stream has finished is an error, never a result.
+static a1mpc_status wait_outputs(a1mpc_handle h, size_t N, size_t armed, const char* path) {
+    if (armed == 0) { A1_HIP(hipStreamSynchronize(h->stream)); return A1MPC_OK; }
+    const char* hout = h->h_pin + h->h_pin_in_bytes;
+    for (unsigned spin = 1; !outputs_landed(hout, N, armed); ++spin) {
+        if ((spin & 0xffff) == 0 && hipStreamQuery(h->stream) != hipErrorNotReady) {   // (about once a millisecond) finished -- the words arrive with it -- or failed
+            A1_HIP(hipStreamSynchronize(h->stream));
+            if (!outputs_landed(hout, N, armed)) return fail(A1MPC_ERR_HIP, std::string(path) + ": the launch finished with output words still in flight");
+            break;
+        }
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#endif
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return A1MPC_OK;
+}
+
+// The pinned block's output region (after wait_outputs, or after the stream has copied a staged launch's outputs into it) into the caller's arrays
+static void host_collect(a1mpc_handle h, size_t N, size_t u_width, double* grf_body_out, double* u_out, int32_t* iters_out, int32_t* status_out) {
+    const HostOut o = host_out_layout(h->h_pin + h->h_pin_in_bytes, N, u_width);
+    std::memcpy(grf_body_out, o.grf, N * 12 * sizeof(double));
+    if (u_out) std::memcpy(u_out, o.u, N * u_width * sizeof(double));
+    if (iters_out) std::memcpy(iters_out, o.iters, N * sizeof(int32_t));
+    if (status_out) std::memcpy(status_out, o.status, N * sizeof(int32_t));
+}
+
 a1mpc_status a1mpc_solve_batch_ticks(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs,
                                      const uint8_t* contact, double* grf_body_out, double* u_full_out, int32_t* iters_out,
                                      int32_t* status_out) {
@@ -2288,10 +2385,14 @@ a1mpc_status a1mpc_solve_batch_ticks(a1mpc_handle h, int32_t n, const double* ti
     A1_HIP(hipSetDevice(h->device));
     const size_t N = n, H = h->cfg.horizon;
     if (H < 2) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "tick records need horizon >= 2");
-    {   // a handful of ticks (the drop-in's compute_grf is n = 1): the kernel reads the handle's pinned block itself, the host polls the outputs (ticks_small_batch)
-        bool taken = false;
-        const a1mpc_status stz = ticks_small_batch(h, n, tick, R_world, foot_abs, contact, grf_body_out, u_full_out, iters_out, status_out, &taken);
-        if (taken) return stz;
+    if (small_batch(h, n)) {   // a handful of ticks (the drop-in's compute_grf is n = 1)
+        const PinnedIn in = pin_inputs(h, {{tick, N * 22 * sizeof(double)}, {R_world, N * 9 * sizeof(double)}, {foot_abs, N * 12 * sizeof(double)}, {contact, N * 4}});
+        const HostOut o = arm_outputs(h, N, u_full_out ? 12 * H : 0);
+        if (a1mpc_status st = a1mpc_solve_batch_ticks_device(h, n, in.f64(0), in.f64(1), in.f64(2), in.u8(3), o.grf, o.u, o.iters, o.status,
+                                                             h->stream); st != A1MPC_OK) return st;
+        if (a1mpc_status st = wait_outputs(h, N, o.bytes, "a1mpc_solve_batch_ticks"); st != A1MPC_OK) return st;
+        host_collect(h, N, 12 * H, grf_body_out, u_full_out, iters_out, status_out);
+        return A1MPC_OK;
     }
     hipStream_t s = h->stream;
     A1_ORDER(h, s);
@@ -2313,142 +2414,30 @@ a1mpc_status a1mpc_solve_batch_ticks(a1mpc_handle h, int32_t n, const double* ti
 }
 
 // The host-pointer MPC entry in two halves, so that a pipeline slot can leave a batch in flight (a1mpc_pipeline_submit):
-//   host_submit   snapshot the caller's arrays into ONE pinned block (the caller's program mutates them concurrently) laid out exactly like the device
-//                 block, one H2D copy, the launches, one D2H copy into the pinned mirror -- all queued on the handle's stream, nothing waited for
-//                 (a tick is one H2D copy, one memset, two launches and one D2H copy -- API calls, not bytes, set batch-1 latency);
-//   host_collect  (after the stream has drained) the pinned mirror into the caller's output arrays.
-constexpr unsigned long long kInFlightWord = 0x7ff85a5a7ff85a5aull;   // what a1mpc_solve_batch leaves in every output word of the pinned block until the kernel has written it (host_submit)
-struct HostOut { size_t q_grf, q_it, q_st, q_u; };
-static HostOut host_out_layout(size_t N) {
-    HostOut o;
-    o.q_grf = 0; o.q_it = o.q_grf + N * 12 * sizeof(double); o.q_st = o.q_it + N * sizeof(int32_t); o.q_u = o.q_st + N * sizeof(int32_t);
-    return o;
-}
+//   host_submit   snapshot the caller's arrays into the pinned block (the caller's program mutates them concurrently) laid out exactly like the device
+//                 block; a small batch is launched on the pinned block itself (*armed: the output bytes armed), a larger one is staged -- one H2D copy,
+//                 the launches, one D2H copy into the pinned mirror (*armed = 0) -- all queued on the handle's stream, nothing waited for;
+//   host_collect  (after wait_outputs) the pinned mirror into the caller's output arrays.
 static a1mpc_status host_submit(a1mpc_handle h, int32_t n, const double* x0, const double* x_ref, const double* R_world, const double* foot_abs,
-                                const uint8_t* contact, bool want_u) {
+                                const uint8_t* contact, bool want_u, size_t* armed) {
     A1_HIP(hipSetDevice(h->device));
     const size_t N = n, H = h->cfg.horizon;
-    const size_t o_x0 = 0, o_xr = o_x0 + N * 13 * sizeof(double), o_R = o_xr + N * 13 * H * sizeof(double),
-                 o_f = o_R + N * 9 * sizeof(double), o_c = o_f + N * 12 * sizeof(double), in_bytes = o_c + N * 4;
-    const HostOut q = host_out_layout(N);
-    const size_t out_bytes = want_u ? q.q_u + N * 12 * H * sizeof(double) : q.q_u;
-    char* hin = h->h_pin;
-    char* hout = h->h_pin + h->h_pin_in_bytes;
-    std::memcpy(hin + o_x0, x0, N * 13 * sizeof(double));
-    std::memcpy(hin + o_xr, x_ref, N * 13 * H * sizeof(double));
-    std::memcpy(hin + o_R, R_world, N * 9 * sizeof(double));
-    std::memcpy(hin + o_f, foot_abs, N * 12 * sizeof(double));
-    std::memcpy(hin + o_c, contact, N * 4);
+    PinnedIn in = pin_inputs(h, {{x0, N * 13 * sizeof(double)}, {x_ref, N * 13 * H * sizeof(double)}, {R_world, N * 9 * sizeof(double)},
+                                 {foot_abs, N * 12 * sizeof(double)}, {contact, N * 4}});
     hipStream_t s = h->stream;
     A1_ORDER(h, s);
-    // Round 5, the batch-1 control tick (BASELINE's latency metric): for a handful of QPs the kernel reads its inputs from, and writes its results to, the handle's
-    // PINNED block itself (device-mapped host memory: 1.3 KB in, ~100 B out per QP over PCIe, a few transactions) -- the two staging copies each cost more on the
-    // GPU's timeline than the bytes they move.  Same kernel, same bits.  A1MPC_ZERO_COPY_MAX (default 8 QPs; 0 = always stage through device memory).
-    static const int zero_copy_max = [] { const char* e = getenv("A1MPC_ZERO_COPY_MAX"); return e ? atoi(e) : 8; }();
-    h->zc_poll_bytes = 0;
-    if (n <= zero_copy_max && h->d_pin != nullptr) {
-        char* din = h->d_pin; char* dout = h->d_pin + h->h_pin_in_bytes;
-        // Round 6: every output word doubles as its own completion flag.  The block the kernel is about to write is filled with a bit pattern no result has (a quiet NaN
-        // with a payload as a double -- forces are finite or exactly zero, a failed solve's u is the payload-free NaN --, 0x7ff85a5a as an int32: no iteration count, no
-        // status), and a1mpc_solve_batch polls until no word holds it any more instead of hipStreamSynchronize(): the host is awake 5 us earlier (p99: 9 us;
-        // tools/ubench/completion_wake_ubench.hip).  No ordering between the kernel's stores is assumed: a first version that polled `status` alone, stored last behind a
-        // system-scope release, saw the forces arrive AFTER it on 2 of 10 000 ticks (posted writes over PCIe with relaxed ordering).
-        static const bool poll = [] { const char* e = getenv("A1MPC_POLL_COMPLETION"); return e ? atoi(e) != 0 : true; }();
-        if (poll) {
-            static_assert(sizeof(unsigned long long) == 8, "");
-            unsigned long long* w = reinterpret_cast<unsigned long long*>(hout);
-            const size_t words = (out_bytes + 7) / 8;
-            for (size_t i = 0; i < words; ++i) w[i] = kInFlightWord;
-            std::atomic_thread_fence(std::memory_order_release);
-            h->zc_poll_bytes = out_bytes;
-        }
-        return a1mpc_solve_batch_device(
-            h, n, reinterpret_cast<const double*>(din + o_x0), reinterpret_cast<const double*>(din + o_xr), reinterpret_cast<const double*>(din + o_R),
-            reinterpret_cast<const double*>(din + o_f), reinterpret_cast<const uint8_t*>(din + o_c), reinterpret_cast<double*>(dout + q.q_grf),
-            want_u ? reinterpret_cast<double*>(dout + q.q_u) : nullptr, reinterpret_cast<int32_t*>(dout + q.q_it), reinterpret_cast<int32_t*>(dout + q.q_st), s);
+    *armed = 0;
+    if (small_batch(h, n)) {
+        const HostOut o = arm_outputs(h, N, want_u ? 12 * H : 0);
+        *armed = o.bytes;
+        return a1mpc_solve_batch_device(h, n, in.f64(0), in.f64(1), in.f64(2), in.f64(3), in.u8(4), o.grf, o.u, o.iters, o.status, s);
     }
-    A1_HIP(hipMemcpyAsync(h->d_in, hin, in_bytes, hipMemcpyHostToDevice, s));
-    a1mpc_status st = a1mpc_solve_batch_device(
-        h, n, reinterpret_cast<const double*>(h->d_in + o_x0), reinterpret_cast<const double*>(h->d_in + o_xr),
-        reinterpret_cast<const double*>(h->d_in + o_R), reinterpret_cast<const double*>(h->d_in + o_f),
-        reinterpret_cast<const uint8_t*>(h->d_in + o_c), reinterpret_cast<double*>(h->d_out + q.q_grf),
-        want_u ? reinterpret_cast<double*>(h->d_out + q.q_u) : nullptr, reinterpret_cast<int32_t*>(h->d_out + q.q_it),
-        reinterpret_cast<int32_t*>(h->d_out + q.q_st), s);
+    A1_HIP(hipMemcpyAsync(h->d_in, h->h_pin, in.bytes, hipMemcpyHostToDevice, s));
+    in.base = h->d_in;
+    const HostOut o = host_out_layout(h->d_out, N, want_u ? 12 * H : 0);
+    a1mpc_status st = a1mpc_solve_batch_device(h, n, in.f64(0), in.f64(1), in.f64(2), in.f64(3), in.u8(4), o.grf, o.u, o.iters, o.status, s);
     if (st != A1MPC_OK) return st;
-    A1_HIP(hipMemcpyAsync(hout, h->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    return A1MPC_OK;
-}
-static void host_collect(a1mpc_handle h, int32_t n, double* grf_body_out, double* u_full_out, int32_t* iters_out, int32_t* status_out) {
-    const size_t N = n, H = h->cfg.horizon;
-    const HostOut q = host_out_layout(N);
-    const char* hout = h->h_pin + h->h_pin_in_bytes;
-    std::memcpy(grf_body_out, hout + q.q_grf, N * 12 * sizeof(double));
-    if (u_full_out) std::memcpy(u_full_out, hout + q.q_u, N * 12 * H * sizeof(double));
-    if (iters_out) std::memcpy(iters_out, hout + q.q_it, N * sizeof(int32_t));
-    if (status_out) std::memcpy(status_out, hout + q.q_st, N * sizeof(int32_t));
-}
-
-// Waits for the outputs of the launch host_submit / ticks_small_batch has just queued: polls the pinned block's output words when the kernel writes them itself
-// (zc_poll_bytes, see host_submit), synchronises the stream otherwise.
-static a1mpc_status host_wait_outputs(a1mpc_handle h, int32_t n) {
-    bool done = false;
-    if (h->zc_poll_bytes) {   // the kernel writes into the pinned block itself: poll its output words (and the stream now and then: a launch that failed never writes them)
-        const HostOut q = host_out_layout(static_cast<size_t>(n));
-        const char* hout = h->h_pin + h->h_pin_in_bytes;
-        const volatile unsigned long long* w64 = reinterpret_cast<const volatile unsigned long long*>(hout);
-        const volatile uint32_t* w32 = reinterpret_cast<const volatile uint32_t*>(hout);
-        const uint32_t lo = static_cast<uint32_t>(kInFlightWord);
-        const size_t i32_first = q.q_it / 4, i32_end = q.q_u / 4, d_end = h->zc_poll_bytes / 8;   // [grf doubles | iters, status int32 | u doubles]
-        for (unsigned spin = 1; !done; ++spin) {
-            done = true;
-            for (size_t i = i32_first; i < i32_end && done; ++i) done = w32[i] != lo;                  // (written last by the kernel: the cheap test first)
-            for (size_t i = 0; i < q.q_it / 8 && done; ++i) done = w64[i] != kInFlightWord;
-            for (size_t i = (q.q_u + 7) / 8; i < d_end && done; ++i) done = w64[i] != kInFlightWord;
-            if (done) break;
-            if ((spin & 0xffff) == 0 && hipStreamQuery(h->stream) != hipErrorNotReady) break;   // (about once a millisecond) finished -- the words arrive with it -- or failed: the synchronisation below reports which
-            __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        h->zc_poll_bytes = 0;
-    }
-    if (!done) A1_HIP(hipStreamSynchronize(h->stream));
-    return A1MPC_OK;
-}
-// a1mpc_solve_batch_ticks for a handful of robots -- what the drop-in's compute_grf calls with n = 1 (include/a1mpc_dropin.hpp) -- the way host_submit serves a1mpc_solve_batch: the
-// tick records, R, feet and contacts are snapshotted into the pinned block, the kernel reads and writes that block itself, the host polls the output words.  (Until round 6's
-// last session this entry always took four pageable host-to-device copies, the launch and up to four copies back.)
-static a1mpc_status ticks_small_batch(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs, const uint8_t* contact, double* grf_body_out,
-                                      double* u_full_out, int32_t* iters_out, int32_t* status_out, bool* taken) {
-    static const int zero_copy_max = [] { const char* e = getenv("A1MPC_ZERO_COPY_MAX"); return e ? atoi(e) : 8; }();
-    *taken = false;
-    if (n > zero_copy_max || h->d_pin == nullptr) return A1MPC_OK;
-    *taken = true;
-    const size_t N = n, H = h->cfg.horizon;
-    const size_t o_t = 0, o_R = o_t + N * 22 * sizeof(double), o_f = o_R + N * 9 * sizeof(double), o_c = o_f + N * 12 * sizeof(double);   // (< h_pin_in_bytes: 43 doubles + 4 bytes per QP)
-    const HostOut q = host_out_layout(N);
-    const bool want_u = u_full_out != nullptr;
-    const size_t out_bytes = want_u ? q.q_u + N * 12 * H * sizeof(double) : q.q_u;
-    char* hin = h->h_pin; char* hout = h->h_pin + h->h_pin_in_bytes;
-    std::memcpy(hin + o_t, tick, N * 22 * sizeof(double));
-    std::memcpy(hin + o_R, R_world, N * 9 * sizeof(double));
-    std::memcpy(hin + o_f, foot_abs, N * 12 * sizeof(double));
-    std::memcpy(hin + o_c, contact, N * 4);
-    h->zc_poll_bytes = 0;
-    static const bool poll = [] { const char* e = getenv("A1MPC_POLL_COMPLETION"); return e ? atoi(e) != 0 : true; }();
-    if (poll) {
-        unsigned long long* w = reinterpret_cast<unsigned long long*>(hout);
-        for (size_t i = 0; i < (out_bytes + 7) / 8; ++i) w[i] = kInFlightWord;
-        std::atomic_thread_fence(std::memory_order_release);
-        h->zc_poll_bytes = out_bytes;
-    }
-    char* din = h->d_pin; char* dout = h->d_pin + h->h_pin_in_bytes;
-    const a1mpc_status st = a1mpc_solve_batch_ticks_device(
-        h, n, reinterpret_cast<const double*>(din + o_t), reinterpret_cast<const double*>(din + o_R), reinterpret_cast<const double*>(din + o_f),
-        reinterpret_cast<const uint8_t*>(din + o_c), reinterpret_cast<double*>(dout + q.q_grf), want_u ? reinterpret_cast<double*>(dout + q.q_u) : nullptr,
-        reinterpret_cast<int32_t*>(dout + q.q_it), reinterpret_cast<int32_t*>(dout + q.q_st), h->stream);
-    if (st != A1MPC_OK) { h->zc_poll_bytes = 0; return st; }
-    if (a1mpc_status sw = host_wait_outputs(h, n); sw != A1MPC_OK) return sw;
-    host_collect(h, n, grf_body_out, u_full_out, iters_out, status_out);
+    A1_HIP(hipMemcpyAsync(h->h_pin + h->h_pin_in_bytes, h->d_out, o.bytes, hipMemcpyDeviceToHost, s));
     return A1MPC_OK;
 }
 
@@ -2460,9 +2449,10 @@ a1mpc_status a1mpc_solve_batch(a1mpc_handle h, int32_t n, const double* x0, cons
         return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
     if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
     if (n == 0) return A1MPC_OK;
-    if (a1mpc_status st = host_submit(h, n, x0, x_ref, R_world, foot_abs, contact, u_full_out != nullptr); st != A1MPC_OK) { h->zc_poll_bytes = 0; return st; }
-    if (a1mpc_status st = host_wait_outputs(h, n); st != A1MPC_OK) return st;
-    host_collect(h, n, grf_body_out, u_full_out, iters_out, status_out);
+    size_t armed = 0;
+    if (a1mpc_status st = host_submit(h, n, x0, x_ref, R_world, foot_abs, contact, u_full_out != nullptr, &armed); st != A1MPC_OK) return st;
+    if (a1mpc_status st = wait_outputs(h, n, armed, "a1mpc_solve_batch"); st != A1MPC_OK) return st;
+    host_collect(h, n, 12 * h->cfg.horizon, grf_body_out, u_full_out, iters_out, status_out);
     return A1MPC_OK;
 }
 
@@ -2575,13 +2565,11 @@ static a1mpc_status strided_host_submit(a1mpc_handle h, int32_t n, const double*
     A1_HIP(hipMemcpyAsync(h->d_foot_steps, foot_abs, N * nfoot * sizeof(double), hipMemcpyHostToDevice, s));
     A1_HIP(hipMemcpyAsync(h->d_contact_steps, contact, N * ncont, hipMemcpyHostToDevice, s));
     if (yaw_A) A1_HIP(hipMemcpyAsync(h->d_aux, yaw_A, N * sizeof(double), hipMemcpyHostToDevice, s));  // d_aux: n x 6 doubles of balance-QP staging, free here
-    const HostOut q = host_out_layout(N);
-    const size_t out_bytes = want_u ? q.q_u + N * 12 * H * sizeof(double) : q.q_u;
-    a1mpc_status st = solve_device_impl(h, n, nullptr, h->d_x0, h->d_xref, h->d_R, h->d_foot_steps, h->d_contact_steps, reinterpret_cast<double*>(h->d_out + q.q_grf),
-                                        want_u ? reinterpret_cast<double*>(h->d_out + q.q_u) : nullptr, reinterpret_cast<int32_t*>(h->d_out + q.q_it),
-                                        reinterpret_cast<int32_t*>(h->d_out + q.q_st), s, foot_stride, contact_stride, yaw_A ? h->d_aux : nullptr);
+    const HostOut o = host_out_layout(h->d_out, N, want_u ? 12 * H : 0);
+    a1mpc_status st = solve_device_impl(h, n, nullptr, h->d_x0, h->d_xref, h->d_R, h->d_foot_steps, h->d_contact_steps, o.grf, o.u, o.iters, o.status, s,
+                                        foot_stride, contact_stride, yaw_A ? h->d_aux : nullptr);
     if (st != A1MPC_OK) return st;
-    A1_HIP(hipMemcpyAsync(h->h_pin + h->h_pin_in_bytes, h->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    A1_HIP(hipMemcpyAsync(h->h_pin + h->h_pin_in_bytes, h->d_out, o.bytes, hipMemcpyDeviceToHost, s));
     return A1MPC_OK;
 }
 a1mpc_status a1mpc_solve_batch_strided(a1mpc_handle h, int32_t n, const double* x0, const double* x_ref, const double* R_world,
@@ -2595,53 +2583,22 @@ a1mpc_status a1mpc_solve_batch_strided(a1mpc_handle h, int32_t n, const double* 
         return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
     if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
     if (n == 0) return A1MPC_OK;
-    {   // A handful of QPs on the general path (the drop-in's ConvexMpc-level call is n = 1): the small-batch path of a1mpc_solve_batch -- inputs in a pinned block the kernel
-        // reads itself (one of its own: per-step feet / contacts do not fit the handle's), outputs in the handle's pinned block, the output words polled.  Until round 6's last
-        // session: five or six pageable copies in, one back, a synchronisation.
-        static const int zero_copy_max = [] { const char* e = getenv("A1MPC_ZERO_COPY_MAX"); return e ? atoi(e) : 8; }();
-        static const bool poll = [] { const char* e = getenv("A1MPC_POLL_COMPLETION"); return e ? atoi(e) != 0 : true; }();
-        if (n <= zero_copy_max && zero_copy_max <= 64 && h->d_pin != nullptr) {
-            A1_HIP(hipSetDevice(h->device));
-            const size_t N = n, H = h->cfg.horizon, M = static_cast<size_t>(zero_copy_max);
-            if (!h->h_pin_gen) {
-                h->h_pin_gen_bytes = M * ((13 + 13 * H + 9 + 12 * H + 1) * sizeof(double) + 4 * H + 8);
-                A1_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_pin_gen), h->h_pin_gen_bytes, hipHostMallocDefault));
-                void* dp = nullptr;
-                if (hipHostGetDevicePointer(&dp, h->h_pin_gen, 0) == hipSuccess) h->d_pin_gen = static_cast<char*>(dp); else (void)hipGetLastError();
-            }
-            if (h->d_pin_gen != nullptr) {
-                const size_t nfoot = foot_stride ? 12 * H : 12, ncont = contact_stride ? 4 * H : 4;
-                const size_t o_x0 = 0, o_xr = o_x0 + N * 13 * sizeof(double), o_R = o_xr + N * 13 * H * sizeof(double), o_f = o_R + N * 9 * sizeof(double),
-                             o_y = o_f + N * nfoot * sizeof(double), o_c = o_y + N * sizeof(double);
-                const HostOut q = host_out_layout(N);
-                const bool want_u = u_full_out != nullptr;
-                const size_t out_bytes = want_u ? q.q_u + N * 12 * H * sizeof(double) : q.q_u;
-                char* hin = h->h_pin_gen; char* hout = h->h_pin + h->h_pin_in_bytes;
-                std::memcpy(hin + o_x0, x0, N * 13 * sizeof(double)); std::memcpy(hin + o_xr, x_ref, N * 13 * H * sizeof(double)); std::memcpy(hin + o_R, R_world, N * 9 * sizeof(double));
-                std::memcpy(hin + o_f, foot_abs, N * nfoot * sizeof(double)); if (yaw_A) std::memcpy(hin + o_y, yaw_A, N * sizeof(double)); std::memcpy(hin + o_c, contact, N * ncont);
-                h->zc_poll_bytes = 0;
-                if (poll) {
-                    unsigned long long* w = reinterpret_cast<unsigned long long*>(hout);
-                    for (size_t i = 0; i < (out_bytes + 7) / 8; ++i) w[i] = kInFlightWord;
-                    std::atomic_thread_fence(std::memory_order_release);
-                    h->zc_poll_bytes = out_bytes;
-                }
-                const char* din = h->d_pin_gen; char* dout = h->d_pin + h->h_pin_in_bytes;
-                const a1mpc_status st = solve_device_impl(
-                    h, n, nullptr, reinterpret_cast<const double*>(din + o_x0), reinterpret_cast<const double*>(din + o_xr), reinterpret_cast<const double*>(din + o_R),
-                    reinterpret_cast<const double*>(din + o_f), reinterpret_cast<const uint8_t*>(din + o_c), reinterpret_cast<double*>(dout + q.q_grf),
-                    want_u ? reinterpret_cast<double*>(dout + q.q_u) : nullptr, reinterpret_cast<int32_t*>(dout + q.q_it), reinterpret_cast<int32_t*>(dout + q.q_st), h->stream,
-                    foot_stride, contact_stride, yaw_A ? reinterpret_cast<const double*>(din + o_y) : nullptr);
-                if (st != A1MPC_OK) { h->zc_poll_bytes = 0; return st; }
-                if (a1mpc_status sw = host_wait_outputs(h, n); sw != A1MPC_OK) return sw;
-                host_collect(h, n, grf_body_out, u_full_out, iters_out, status_out);
-                return A1MPC_OK;
-            }
-        }
+    const size_t N = n, H = h->cfg.horizon;
+    if (N <= small_general_max() && h->d_pin != nullptr) {   // a handful of QPs on the general path (the drop-in's ConvexMpc-level call is n = 1)
+        A1_HIP(hipSetDevice(h->device));
+        const size_t nfoot = foot_stride ? 12 * H : 12, ncont = contact_stride ? 4 * H : 4;
+        const PinnedIn in = pin_inputs(h, {{x0, N * 13 * sizeof(double)}, {x_ref, N * 13 * H * sizeof(double)}, {R_world, N * 9 * sizeof(double)},
+                                           {foot_abs, N * nfoot * sizeof(double)}, {yaw_A, N * sizeof(double)}, {contact, N * ncont}});
+        const HostOut o = arm_outputs(h, N, u_full_out ? 12 * H : 0);
+        if (a1mpc_status st = solve_device_impl(h, n, nullptr, in.f64(0), in.f64(1), in.f64(2), in.f64(3), in.u8(5), o.grf, o.u, o.iters,
+                                                o.status, h->stream, foot_stride, contact_stride, in.f64(4)); st != A1MPC_OK) return st;
+        if (a1mpc_status st = wait_outputs(h, N, o.bytes, "a1mpc_solve_batch_strided (general path)"); st != A1MPC_OK) return st;
+        host_collect(h, N, 12 * H, grf_body_out, u_full_out, iters_out, status_out);
+        return A1MPC_OK;
     }
     if (a1mpc_status st = strided_host_submit(h, n, x0, x_ref, R_world, foot_abs, foot_stride, contact, contact_stride, yaw_A, u_full_out != nullptr); st != A1MPC_OK) return st;
     A1_HIP(hipStreamSynchronize(h->stream));
-    host_collect(h, n, grf_body_out, u_full_out, iters_out, status_out);
+    host_collect(h, N, 12 * H, grf_body_out, u_full_out, iters_out, status_out);
     return A1MPC_OK;
 }
 a1mpc_status a1mpc_balance_solve_batch(a1mpc_handle h, const a1mpc_balance_config* qp, int32_t n, const double* root_acc,
@@ -2657,33 +2614,6 @@ a1mpc_status a1mpc_balance_solve_batch(a1mpc_handle h, const a1mpc_balance_confi
     const size_t N = n;
     hipStream_t s = h->stream;
     A1_ORDER(h, s);
-    // A handful of QPs (the drop-in's compute_grf with stance_leg_control_type = 0 is n = 1): inputs and outputs in the handle's pinned block, read and written by the kernel
-    // itself, the output words polled -- the small-batch path of a1mpc_solve_batch (host_submit).  Larger batches: the transfers are small (344 B per QP); pageable copies on
-    // the stream are synchronous w.r.t. the host buffer
-    static const int zero_copy_max = [] { const char* e = getenv("A1MPC_ZERO_COPY_MAX"); return e ? atoi(e) : 8; }();
-    static const bool poll = [] { const char* e = getenv("A1MPC_POLL_COMPLETION"); return e ? atoi(e) != 0 : true; }();
-    const bool small = n <= zero_copy_max && h->d_pin != nullptr;
-    const size_t o_a = 0, o_R = o_a + N * 6 * sizeof(double), o_Rz = o_R + N * 9 * sizeof(double), o_f = o_Rz + N * 9 * sizeof(double), o_c = o_f + N * 12 * sizeof(double);
-    const HostOut q = host_out_layout(N);
-    const size_t out_bytes = f_world_out ? q.q_u + N * 12 * sizeof(double) : q.q_u;
-    h->zc_poll_bytes = 0;
-    if (small) {
-        char* hin = h->h_pin; char* hout = h->h_pin + h->h_pin_in_bytes;
-        std::memcpy(hin + o_a, root_acc, N * 6 * sizeof(double)); std::memcpy(hin + o_R, R_world, N * 9 * sizeof(double)); std::memcpy(hin + o_Rz, R_z, N * 9 * sizeof(double));
-        std::memcpy(hin + o_f, foot_abs, N * 12 * sizeof(double)); std::memcpy(hin + o_c, contact, N * 4);
-        if (poll) {
-            unsigned long long* w = reinterpret_cast<unsigned long long*>(hout);
-            for (size_t i = 0; i < (out_bytes + 7) / 8; ++i) w[i] = kInFlightWord;
-            std::atomic_thread_fence(std::memory_order_release);
-            h->zc_poll_bytes = out_bytes;
-        }
-    } else {
-        A1_HIP(hipMemcpyAsync(h->d_aux, root_acc, N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-        A1_HIP(hipMemcpyAsync(h->d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-        A1_HIP(hipMemcpyAsync(h->d_Rz, R_z, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-        A1_HIP(hipMemcpyAsync(h->d_foot, foot_abs, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-        A1_HIP(hipMemcpyAsync(h->d_contact, contact, N * 4, hipMemcpyHostToDevice, s));
-    }
     KernelArgs a;
     std::memset(&a, 0, sizeof a);
     a.P = h->dp;
@@ -2691,30 +2621,34 @@ a1mpc_status a1mpc_balance_solve_batch(a1mpc_handle h, const a1mpc_balance_confi
     a.P.dt = 0.0; a.P.mu = qp->mu; a.P.fz_min = qp->F_min; a.P.fz_max = qp->F_max; a.P.warm_start = 0;
     for (int i = 0; i < 12; ++i) { a.P.q2[i] = 0.0; a.P.r2[i] = qp->R; }
     for (int k = 0; k < 3; ++k) { a.P.q2[6 + k] = qp->Q[3 + k]; a.P.q2[9 + k] = qp->Q[k]; }
-    a.tab = h->d_tab1; a.n = n;
-    a.root_acc = h->d_aux; a.Rz = h->d_Rz; a.R = h->d_R; a.foot = h->d_foot; a.contact = h->d_contact;
-    a.grf = h->d_grf; a.u_full = h->d_u; a.iters = h->d_iters; a.status = h->d_status; a.nfact = h->d_nfact;
-    if (small) {
-        const char* din = h->d_pin; char* dout = h->d_pin + h->h_pin_in_bytes;
-        a.root_acc = reinterpret_cast<const double*>(din + o_a); a.R = reinterpret_cast<const double*>(din + o_R); a.Rz = reinterpret_cast<const double*>(din + o_Rz);
-        a.foot = reinterpret_cast<const double*>(din + o_f); a.contact = reinterpret_cast<const uint8_t*>(din + o_c);
-        a.grf = reinterpret_cast<double*>(dout + q.q_grf); a.u_full = f_world_out ? reinterpret_cast<double*>(dout + q.q_u) : nullptr;
-        a.iters = reinterpret_cast<int32_t*>(dout + q.q_it); a.status = reinterpret_cast<int32_t*>(dout + q.q_st);
+    a.tab = h->d_tab1; a.n = n; a.nfact = h->d_nfact;
+    size_t armed = 0;
+    if (small_batch(h, n)) {   // a handful of QPs (the drop-in's compute_grf with stance_leg_control_type = 0 is n = 1)
+        const PinnedIn in = pin_inputs(h, {{root_acc, N * 6 * sizeof(double)}, {R_world, N * 9 * sizeof(double)}, {R_z, N * 9 * sizeof(double)},
+                                           {foot_abs, N * 12 * sizeof(double)}, {contact, N * 4}});
+        const HostOut o = arm_outputs(h, N, f_world_out ? 12 : 0);
+        a.root_acc = in.f64(0); a.R = in.f64(1); a.Rz = in.f64(2); a.foot = in.f64(3); a.contact = in.u8(4);
+        a.grf = o.grf; a.u_full = o.u; a.iters = o.iters; a.status = o.status;
+        armed = o.bytes;
+    } else {   // larger batches: the transfers are small (344 B per QP); pageable copies on the stream are synchronous w.r.t. the host buffer
+        A1_HIP(hipMemcpyAsync(h->d_aux, root_acc, N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+        A1_HIP(hipMemcpyAsync(h->d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+        A1_HIP(hipMemcpyAsync(h->d_Rz, R_z, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+        A1_HIP(hipMemcpyAsync(h->d_foot, foot_abs, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+        A1_HIP(hipMemcpyAsync(h->d_contact, contact, N * 4, hipMemcpyHostToDevice, s));
+        a.root_acc = h->d_aux; a.Rz = h->d_Rz; a.R = h->d_R; a.foot = h->d_foot; a.contact = h->d_contact;
+        a.grf = h->d_grf; a.u_full = h->d_u; a.iters = h->d_iters; a.status = h->d_status;
     }
     if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
     h->staged = false;
     a1mpc_status st = launch<1, kModeBalance>(a, s);
-    if (st != A1MPC_OK) { h->zc_poll_bytes = 0; return st; }
+    if (st != A1MPC_OK) return st;
     if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
     h->timed = h->timing;
     A1_MARK(h, s);
-    if (small) {
-        if (a1mpc_status sw = host_wait_outputs(h, n); sw != A1MPC_OK) return sw;
-        const char* hout = h->h_pin + h->h_pin_in_bytes;
-        std::memcpy(grf_body_out, hout + q.q_grf, N * 12 * sizeof(double));
-        if (f_world_out) std::memcpy(f_world_out, hout + q.q_u, N * 12 * sizeof(double));
-        if (iters_out) std::memcpy(iters_out, hout + q.q_it, N * sizeof(int32_t));
-        if (status_out) std::memcpy(status_out, hout + q.q_st, N * sizeof(int32_t));
+    if (armed) {
+        if (a1mpc_status sw = wait_outputs(h, N, armed, "a1mpc_balance_solve_batch"); sw != A1MPC_OK) return sw;
+        host_collect(h, N, 12, grf_body_out, f_world_out, iters_out, status_out);
         return A1MPC_OK;
     }
     A1_HIP(hipMemcpyAsync(grf_body_out, h->d_grf, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3163,7 +3097,7 @@ static a1mpc_status pipeline_deliver(a1mpc_pipeline p, int k) {
     a1mpc_pipeline_s::HostPending& q = p->pending[k];
     if (q.n == 0) return A1MPC_OK;
     A1_HIP(hipStreamSynchronize(p->h[k]->stream));   // (the slot's stream carries nothing but this batch; the wait a1mpc_solve_batch uses)
-    host_collect(p->h[k], q.n, q.grf, q.u, q.iters, q.status);
+    host_collect(p->h[k], q.n, 12 * p->h[k]->cfg.horizon, q.grf, q.u, q.iters, q.status);
     q = a1mpc_pipeline_s::HostPending();
     return A1MPC_OK;
 }
@@ -3336,7 +3270,8 @@ a1mpc_status a1mpc_pipeline_submit(a1mpc_pipeline p, int32_t slot, int32_t fresh
     if (slot < 0) p->next = (p->next + 1) % p->depth;
     if (n == 0) return A1MPC_OK;
     if (fresh_batch) h->hint_n = 0;
-    if (a1mpc_status st = host_submit(h, n, x0, x_ref, R_world, foot_abs, contact, u_full_out != nullptr); st != A1MPC_OK) return st;
+    size_t armed;   // (unused: pipeline_deliver synchronises the slot's stream)
+    if (a1mpc_status st = host_submit(h, n, x0, x_ref, R_world, foot_abs, contact, u_full_out != nullptr, &armed); st != A1MPC_OK) return st;
     A1_HIP(hipEventRecord(p->done[k], h->stream));
     p->used[k] = 1;
     a1mpc_pipeline_s::HostPending& q = p->pending[k];

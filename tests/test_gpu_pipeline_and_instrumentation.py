@@ -258,6 +258,15 @@ def test_host_pointer_pipeline_matches_the_synchronous_entry(pkg, scen):
             with pkg.Engine(cfg, m, 0) as small:
                 r = small.solve(scs[1]["x0"][:m], scs[1]["xref"][:m], scs[1]["R"][:m], scs[1]["foot"][:m], scs[1]["contact"][:m])
             assert np.array_equal(o["grf"], r["grf"])
+            # m <= A1MPC_ZERO_COPY_MAX: the kernel writes the in-flight slot's pinned mirror itself, pipeline_wait delivers it
+            m = 5
+            o = dict(grf=np.zeros((m, 12)), u=np.zeros((m, 120)), iters=np.full(m, -1, np.int32), status=np.full(m, -99, np.int32))
+            pipe.submit(scs[2]["x0"][:m], scs[2]["xref"][:m], scs[2]["R"][:m], scs[2]["foot"][:m], scs[2]["contact"][:m], o, slot=1)
+            pipe.wait(1)
+            with pkg.Engine(cfg, m, 0) as small:
+                r = small.solve(scs[2]["x0"][:m], scs[2]["xref"][:m], scs[2]["R"][:m], scs[2]["foot"][:m], scs[2]["contact"][:m], want_u=True)
+            assert np.array_equal(o["grf"], r["grf"]) and np.array_equal(o["u"], r["u"]), depth
+            assert np.array_equal(o["iters"], r["iters"]) and np.array_equal(o["status"], r["status"]), depth
             e = dict(grf=np.zeros((0, 12)))
             pipe.submit(scs[1]["x0"][:0], scs[1]["xref"][:0], scs[1]["R"][:0], scs[1]["foot"][:0], scs[1]["contact"][:0], e, slot=1)
             pipe.wait()

@@ -1,6 +1,6 @@
 import gc, os, sys, time, importlib
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
 pkg = g.load_package(); scen = pkg.scenarios
 gc.collect(); gc.disable()

@@ -23,4 +23,4 @@ for name in ("solve_ticks", "solve"):
             else: r = eng.solve(sc["x0"][t], sc["xref"][t], sc["R"][t], sc["foot"][t], sc["contact"][t])
             lat[t] = time.perf_counter() - a
     l = lat[100:] * 1e3
-    print(f"{name:12s} zero_copy_max={os.environ.get('A1MPC_ZERO_COPY_MAX', '8')} poll={os.environ.get('A1MPC_POLL_COMPLETION', '1')}: p50 {np.percentile(l, 50):.4f} ms  p99 {np.percentile(l, 99):.4f} ms  (ctypes call included)")
+    print(f"{name:12s} zero_copy_max={os.environ.get('A1MPC_ZERO_COPY_MAX', '8')}: p50 {np.percentile(l, 50):.4f} ms  p99 {np.percentile(l, 99):.4f} ms  (ctypes call included)")
