@@ -265,6 +265,79 @@ __global__ __launch_bounds__(256) void a1mpc_plan_kernel(const PlanArgs a) {
     ws.flush3(rel, ab, wo, a.rel, a.abs_, a.world);   // (the three [robot][12] outputs leave through the wave's LDS stage: WaveStage)
 }
 
+// ---- the gait-aware horizon (a1mpc_horizon_preview_batch): the contact schedule and the per-step feet that a1mpc_solve_batch_strided takes, produced from the
+// state a control tick holds on the device.  One lane per (robot, leg), like the plan kernel; no LDS.  No FMA contraction: schedule and feet are bit-identical
+// to the C++ they restate (update_plan's counter rule, S/A1RobotControl.cpp:156-164, run forward; the foot recurrence of S/test/test_mpc.cpp:112-115).
+//   schedule  a lane runs its leg's counter forward -- c = fmod(c + speed, counter_per_gait), ticks_per_step times per horizon step, iterated like update_plan itself
+//             will, so step t IS the plan_contacts of t * ticks_per_step ticks from now -- and keeps the H contact bits in one register; the four lanes of a robot
+//             exchange their registers and lane `leg` stores steps leg, leg + 4, ... as whole 4-byte words (the robot's four lanes: 16 consecutive bytes per store)
+//   feet      f_0 = foot_pos_abs, f_(t+1) = f_t - (v * dt): the product is rounded first, then subtracted; v = root_lin_vel_d (mode 1) or R_world * root_lin_vel_d (mode 2)
+struct PreviewArgs {
+    int32_t n, H, ticks_per_step;
+    int32_t sched_mode;   // 0: contacts[] at every step (the reference's broadcast written out), 1: the gait's schedule
+    int32_t foot_mode;    // 1: body-frame command as the reference's lines have it, 2: world-frame command
+    double counter_per_gait, counter_per_swing, dt;
+    const uint8_t *movement_mode, *contacts;
+    const double *gait_counter, *gait_counter_speed, *foot_pos_abs, *Rw, *root_lin_vel_d;
+    uint32_t* sched;      // n x H words (4 contact bytes each), or null
+    double* foot_steps;   // n x 12H, or null
+};
+__global__ __launch_bounds__(256) void a1mpc_horizon_preview_kernel(const PreviewArgs a) {
+#pragma clang fp contract(off)
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const int64_t b = gid >> 2;
+    const int leg = static_cast<int>(gid & 3);
+    const bool live = b < a.n;
+    const int H = a.H;
+    if (a.sched != nullptr) {
+        uint32_t m = 0;   // bit t: my leg is in contact at horizon step t
+        if (live) {
+            const uint32_t all = (1u << H) - 1u;   // (H <= 20)
+            const uint32_t c0 = a.contacts[b * 4 + leg] ? 1u : 0u;   // step 0: the actual contacts[] (S/A1RobotControl.cpp:271), the value the reference broadcasts
+            if (a.sched_mode == 0) m = c0 ? all : 0u;
+            else if (!a.movement_mode[b]) m = c0 | (all & ~1u);   // stand: every planned contact is 1 (:150-153)
+            else {
+                double c = a.gait_counter[b * 4 + leg];
+                const double spd = a.gait_counter_speed[b * 4 + leg];
+                m = c0;
+                for (int t = 1; t < H; ++t) {
+                    for (int k = 0; k < a.ticks_per_step; ++k) {   // :158-159, one control tick
+                        c = c + spd;
+                        c = fmod(c, a.counter_per_gait);
+                    }
+                    m |= (c <= a.counter_per_swing ? 1u : 0u) << t;   // :160-164
+                }
+            }
+        }
+        const int q0 = lane & ~3;   // (every lane of the wavefront takes part in the exchange: no lane has left)
+        const uint32_t m0 = __shfl(m, q0, 64), m1 = __shfl(m, q0 + 1, 64), m2 = __shfl(m, q0 + 2, 64), m3 = __shfl(m, q0 + 3, 64);
+        if (live) {
+            uint32_t* out = a.sched + b * H;
+            for (int t = leg; t < H; t += 4)
+                out[t] = ((m0 >> t) & 1u) | (((m1 >> t) & 1u) << 8) | (((m2 >> t) & 1u) << 16) | (((m3 >> t) & 1u) << 24);
+        }
+    }
+    if (a.foot_steps != nullptr && live) {
+        const double* vd = a.root_lin_vel_d + b * 3;
+        double v[3] = {vd[0], vd[1], vd[2]};
+        if (a.foot_mode == 2) {   // root_lin_vel_d_world = root_rot_mat * root_lin_vel_d (S/A1RobotControl.cpp:470)
+            const double* R = a.Rw + b * 9;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) v[r] = R[r * 3 + 0] * vd[0] + R[r * 3 + 1] * vd[1] + R[r * 3 + 2] * vd[2];
+        }
+        const double* f0 = a.foot_pos_abs + b * 12 + 3 * leg;
+        double f[3] = {f0[0], f0[1], f0[2]};
+        const double st[3] = {v[0] * a.dt, v[1] * a.dt, v[2] * a.dt};   // root_lin_vel_d * dt: the same product at every step
+        double* out = a.foot_steps + b * 12 * H + 3 * leg;
+        for (int t = 0; t < H; ++t) {
+            out[0] = f[0]; out[1] = f[1]; out[2] = f[2];
+            f[0] = f[0] - st[0]; f[1] = f[1] - st[1]; f[2] = f[2] - st[2];   // S/test/test_mpc.cpp:112-115
+            out += 12;
+        }
+    }
+}
+
 thread_local std::string g_last_error;
 std::mutex g_cache_mu;
 thread_local bool g_clk_ran = false;
@@ -522,6 +595,8 @@ struct a1mpc_handle_s {
     double* d_ct_state = nullptr;  // N2b filter state of every robot (allocated on first use)
     double* d_ekf_state = nullptr;  // N4c Kalman filter state of every robot (allocated on first use)
     double* d_tickrec = nullptr;    // a1mpc_control_tick_device: n x 22 tick records + 3 doubles (km_foot), allocated on first use
+    uint32_t* d_pv_sched = nullptr; // a1mpc_control_tick_preview_device: n x H words, the horizon's contact schedule (allocated on first use)
+    double* d_pv_foot = nullptr;    // ... and n x 12H per-step feet (allocated on first use)
     int32_t ekf_ready_n = 0;        // robots 0 .. ekf_ready_n - 1 have had their filter initialised (the init kernel is not launched for them again)
     // staging of the element-wise entry points (N2a, N2b, N3), allocated on first use: 64 / 96 doubles and 16 bytes per robot
     double *d_aux_in = nullptr, *d_aux_out = nullptr;
@@ -1688,7 +1763,7 @@ void a1mpc_destroy(a1mpc_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_tab, h->d_tab1, h->d_x0, h->d_xref, h->d_R, h->d_foot, h->d_aux, h->d_Rz, h->d_contact, h->d_grf,
-                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec};
+                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -2060,7 +2135,8 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
     h->last_ws_mode = (h->cfg.warm_start == 2 && a.carry == nullptr) ? 1 : h->cfg.warm_start;   // (the general path's split pipeline revises this below)
     a.contact_stride = contact_stride;  // a per-step contact schedule alone (feet step-invariant) stays on the fast path: contacts only change bounds and equality rows
     if (foot_stride != 0 || d_yaw_A != nullptr) {  // general path: per-step B_d (and / or its own A_c yaw), with or without a contact schedule
-        if (d_tick) return fail(A1MPC_ERR_INVALID_ARGUMENT, "per-step feet / contacts are not combined with tick records");
+        // (tick records too -- a1mpc_solve_batch_ticks_strided: RowSolver::setup builds x0 / x_ref from the record in the GEN instantiations as on the fast path, and
+        // a1mpc_predict_kernel reads either form; nothing else of the general path touches x0 / x_ref)
         a.foot_stride = foot_stride; a.contact_stride = contact_stride; a.yaw_A = d_yaw_A;
         // a batch beyond the resident rows of the general path's ADMM kernel runs its split pipeline (set-up kernel + persistent rows on a queue, like the
         // fast path); its hand-off records (B~w_t of every step included) live in a buffer of their own, allocated on first use
@@ -2164,6 +2240,127 @@ a1mpc_status a1mpc_solve_batch_ticks_device(a1mpc_handle h, int32_t n, const dou
                              d_status_out, hip_stream);
 }
 
+static bool strides_ok(int32_t foot_stride, int32_t contact_stride) {
+    return (foot_stride == 0 || foot_stride == 12) && (contact_stride == 0 || contact_stride == 4);
+}
+// Tick records joined with the strides of a1mpc_solve_batch_strided: (0, 0, NULL) is a1mpc_solve_batch_ticks_device, (0, 4, NULL) the fast kernels with a schedule,
+// per-step feet / a yaw_A the general kernels -- all of them build x0 / x_ref from the record in their set-up (RowSolver::setup)
+a1mpc_status a1mpc_solve_batch_ticks_strided_device(a1mpc_handle h, int32_t n, const double* d_tick, const double* d_R_world, const double* d_foot_abs,
+                                                    int32_t foot_stride, const uint8_t* d_contact, int32_t contact_stride, const double* d_yaw_A,
+                                                    double* d_grf_body_out, double* d_u_full_out, int32_t* d_iters_out, int32_t* d_status_out, void* hip_stream) {
+    if (!d_tick) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
+    if (!strides_ok(foot_stride, contact_stride)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "foot_stride must be 0 or 12, contact_stride 0 or 4");
+    if (h && h->cfg.horizon < 2) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "tick records need horizon >= 2");
+    return solve_device_impl(h, n, d_tick, nullptr, nullptr, d_R_world, d_foot_abs, d_contact, d_grf_body_out, d_u_full_out, d_iters_out, d_status_out, hip_stream,
+                             foot_stride, contact_stride, d_yaw_A);
+}
+
+// ---- the gait-aware horizon: a1mpc_horizon_preview_kernel behind the C ABI
+void a1mpc_default_preview_config(a1mpc_preview_config* c) {
+    if (!c) return;
+    c->contact_schedule = 1; c->foot_preview = 0; c->ticks_per_step = 1;
+}
+// what a1mpc_horizon_preview_batch(_device) and a1mpc_control_tick_preview_device refuse, or null
+static const char* invalid_preview(a1mpc_handle h, const a1mpc_preview_config* pv) {
+    if (!h) return "null handle";
+    if (!pv) return "null a1mpc_preview_config";
+    if (pv->ticks_per_step < 1 || pv->ticks_per_step > 64) return "a1mpc_preview_config.ticks_per_step must be 1..64";
+    if (pv->foot_preview < 0 || pv->foot_preview > 2) return "a1mpc_preview_config.foot_preview must be 0, 1 or 2";
+    if (pv->contact_schedule < 0 || pv->contact_schedule > 1) return "a1mpc_preview_config.contact_schedule must be 0 or 1";
+    if (h->cfg.horizon < 2) return "a horizon preview needs horizon >= 2 (a1mpc_config.horizon)";
+    return nullptr;
+}
+// the launch alone (arguments validated by the caller, which also orders and marks the stream)
+static void launch_preview(a1mpc_handle h, const a1mpc_preview_config& pv, double counter_per_gait, double counter_per_swing, int32_t n, const uint8_t* movement_mode,
+                           const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs, const double* R_world,
+                           const double* root_lin_vel_d, uint8_t* sched_out, double* foot_steps_out, hipStream_t s) {
+    PreviewArgs a;
+    a.n = n; a.H = h->cfg.horizon; a.ticks_per_step = pv.ticks_per_step; a.sched_mode = pv.contact_schedule; a.foot_mode = pv.foot_preview;
+    a.counter_per_gait = counter_per_gait; a.counter_per_swing = counter_per_swing; a.dt = h->cfg.dt;
+    a.movement_mode = movement_mode; a.contacts = contacts; a.gait_counter = gait_counter; a.gait_counter_speed = gait_counter_speed;
+    a.foot_pos_abs = foot_pos_abs; a.Rw = R_world; a.root_lin_vel_d = root_lin_vel_d;
+    a.sched = reinterpret_cast<uint32_t*>(sched_out); a.foot_steps = foot_steps_out;
+    hipLaunchKernelGGL(a1mpc_horizon_preview_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) * 4 + 255) / 256)), dim3(256), 0, s, a);
+}
+// pointer rules shared by the two preview entries: each output needs its inputs
+static const char* invalid_preview_io(const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, const uint8_t* movement_mode, const double* gait_counter,
+                                      const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs, const double* R_world,
+                                      const double* root_lin_vel_d, const uint8_t* sched_out, const double* foot_steps_out, bool device) {
+    if (!gait) return "null a1mpc_gait_config";
+    if (!(gait->counter_per_gait > 0)) return "a1mpc_gait_config.counter_per_gait <= 0";
+    if (!sched_out && !foot_steps_out) return "null input/output pointer";
+    if (sched_out && (!contacts || (pv->contact_schedule == 1 && (!movement_mode || !gait_counter || !gait_counter_speed)))) return "null input/output pointer";
+    if (foot_steps_out && pv->foot_preview == 0) return "foot_steps_out needs a1mpc_preview_config.foot_preview 1 or 2";
+    if (foot_steps_out && (!foot_pos_abs || !root_lin_vel_d || (pv->foot_preview == 2 && !R_world))) return "null input/output pointer";
+    if (device && (reinterpret_cast<uintptr_t>(sched_out) & 3u)) return "contact_sched_out must be 4-byte aligned (it is written one horizon step, four contact bytes, at a time)";
+    return nullptr;
+}
+a1mpc_status a1mpc_horizon_preview_batch_device(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n,
+                                                const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts,
+                                                const double* foot_pos_abs, const double* R_world, const double* root_lin_vel_d, uint8_t* sched_out,
+                                                double* foot_steps_out, void* hip_stream) {
+    if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
+    if (const char* bad = invalid_preview_io(pv, gait, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, sched_out, foot_steps_out, true))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
+    if (n == 0) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
+    A1_ORDER(h, s);
+    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
+    launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d,
+                   sched_out, foot_steps_out, s);
+    A1_HIP(hipGetLastError());
+    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
+    h->timed = h->timing; A1_MARK(h, s);
+    return A1MPC_OK;
+}
+// the handle's per-step staging (a1mpc_solve_batch_strided's too): n x 12H feet, n x 4H contact bytes
+static a1mpc_status ensure_step_staging(a1mpc_handle h) {
+    if (h->d_foot_steps) return A1MPC_OK;
+    const size_t H = h->cfg.horizon;
+    A1_HIP(hipMalloc(&h->d_foot_steps, static_cast<size_t>(h->max_batch) * 12 * H * sizeof(double)));
+    A1_HIP(hipMalloc(&h->d_contact_steps, static_cast<size_t>(h->max_batch) * 4 * H));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_horizon_preview_batch(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
+                                         const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs,
+                                         const double* R_world, const double* root_lin_vel_d, uint8_t* sched_out, double* foot_steps_out) {
+    if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
+    if (const char* bad = invalid_preview_io(pv, gait, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, sched_out, foot_steps_out,
+                                             false)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);   // (a host array for the schedule may sit at any address: it is staged)
+    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
+    if (n == 0) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
+    if (a1mpc_status st = ensure_step_staging(h); st != A1MPC_OK) return st;
+    const size_t N = n, H = h->cfg.horizon;
+    hipStream_t s = h->stream;
+    A1_ORDER(h, s);
+    // staging: in [gc 4 | spd 4 | foot 12 | R 9 | vd 3] + bytes [mode 1 .. | contacts 4 from 8 N], out: the handle's per-step buffers
+    double *d_gc = h->d_aux_in, *d_spd = d_gc + 4 * N, *d_fp = d_spd + 4 * N, *d_R = d_fp + 12 * N, *d_vd = d_R + 9 * N;
+    uint8_t *d_mm = h->d_aux_u8, *d_ct = h->d_aux_u8 + 8 * N;
+    if (gait_counter) A1_HIP(hipMemcpyAsync(d_gc, gait_counter, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (gait_counter_speed) A1_HIP(hipMemcpyAsync(d_spd, gait_counter_speed, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (foot_pos_abs) A1_HIP(hipMemcpyAsync(d_fp, foot_pos_abs, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (R_world) A1_HIP(hipMemcpyAsync(d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (root_lin_vel_d) A1_HIP(hipMemcpyAsync(d_vd, root_lin_vel_d, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (movement_mode) A1_HIP(hipMemcpyAsync(d_mm, movement_mode, N, hipMemcpyHostToDevice, s));
+    if (contacts) A1_HIP(hipMemcpyAsync(d_ct, contacts, N * 4, hipMemcpyHostToDevice, s));
+    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
+    launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, d_mm, d_gc, d_spd, d_ct, d_fp, d_R, d_vd, sched_out ? h->d_contact_steps : nullptr,
+                   foot_steps_out ? h->d_foot_steps : nullptr, s);
+    A1_HIP(hipGetLastError());
+    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
+    h->timed = h->timing; A1_MARK(h, s);
+    if (sched_out) A1_HIP(hipMemcpyAsync(sched_out, h->d_contact_steps, N * 4 * H, hipMemcpyDeviceToHost, s));
+    if (foot_steps_out) A1_HIP(hipMemcpyAsync(foot_steps_out, h->d_foot_steps, N * 12 * H * sizeof(double), hipMemcpyDeviceToHost, s));
+    A1_HIP(hipStreamSynchronize(s));
+    return A1MPC_OK;
+}
+
 void a1mpc_default_tick_params(a1mpc_tick_params* p) {
     if (!p) return;
     std::memset(p, 0, sizeof *p);
@@ -2182,8 +2379,11 @@ void a1mpc_default_tick_params(a1mpc_tick_params* p) {
 // the terrain fit of compute_grf :335-376) -> compute_grf (:446-562) -> compute_joint_torques (:289-319), as driven by S/MainGazebo.cpp:47-119 -- six kernels, the tick-record
 // pack and the MPC launch back to back on one stream, no host round trip, and N3 inside the MPC kernel's output stage whenever the tick runs the fused / latency kernel
 // (every warm-started tick of a known batch).  Bit-identical to chaining the seven *_device entry points.
-a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
+// pv: the gait-aware horizon (a1mpc_control_tick_preview_device), or null / {0, 0, *}: the plain tick -- the same launches as before the preview existed
+static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
     if (!h || !p || !bf) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle / params / buffers");
+    const bool pv_sched = pv != nullptr && pv->contact_schedule == 1, pv_feet = pv != nullptr && pv->foot_preview != 0;
+    if ((pv_sched || pv_feet) && !(p->gait.counter_per_gait > 0)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "a1mpc_gait_config.counter_per_gait <= 0");
     if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
     if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
     if (h->cfg.horizon < 2) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "tick records need horizon >= 2");
@@ -2200,6 +2400,8 @@ a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* 
     A1_ORDER(h, s);
     const size_t N = n;
     if (!h->d_tickrec) A1_HIP(hipMalloc(&h->d_tickrec, (static_cast<size_t>(h->max_batch) * 22 + 3) * sizeof(double)));
+    if (pv_sched && !h->d_pv_sched) A1_HIP(hipMalloc(&h->d_pv_sched, static_cast<size_t>(h->max_batch) * h->cfg.horizon * sizeof(uint32_t)));
+    if (pv_feet && !h->d_pv_foot) A1_HIP(hipMalloc(&h->d_pv_foot, static_cast<size_t>(h->max_batch) * 12 * h->cfg.horizon * sizeof(double)));
     if (!h->d_ekf_state) {
         A1_HIP(hipMalloc(&h->d_ekf_state, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double)));
         A1_HIP(hipMemsetAsync(h->d_ekf_state, 0, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double), s));
@@ -2259,9 +2461,20 @@ a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* 
         A1_HIP(hipMemcpyAsync(d_km, h->h_pin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
         A1_HIP(hipStreamSynchronize(s));   // (once: the pinned words may be overwritten by a later host-pointer call)
     }
-    // 7. MPC from the tick records + N3 in its output stage
+    // 6b. the gait-aware horizon: the contact schedule (step 0 = the contacts stage 5 has just written) and / or the per-step feet, into the handle's buffers
+    const double* mpc_foot = bf->foot_pos_abs; const uint8_t* mpc_contact = bf->contacts;
+    if (pv_sched || pv_feet) {
+        launch_preview(h, *pv, p->gait.counter_per_gait, p->gait.counter_per_swing, n, bf->movement_mode, bf->gait_counter, bf->gait_counter_speed, bf->contacts, bf->foot_pos_abs,
+                       bf->R_world, bf->root_lin_vel_d, pv_sched ? reinterpret_cast<uint8_t*>(h->d_pv_sched) : nullptr, pv_feet ? h->d_pv_foot : nullptr, s);
+        A1_HIP(hipGetLastError());
+        if (pv_sched) mpc_contact = reinterpret_cast<const uint8_t*>(h->d_pv_sched);
+        if (pv_feet) mpc_foot = h->d_pv_foot;
+    }
+    // 7. MPC from the tick records + N3 in its output stage (fast kernels: with a schedule that stage reads step 0, the actual contacts; the general kernels -- per-step
+    //    feet -- have no such stage and leave `fused` false)
     TorqueFuse tq{bf->mpc_active, bf->j_foot_blocks, bf->foot_forces_kin, bf->torques_gravity, d_km, bf->joint_torques, false};
-    if (a1mpc_status st = solve_device_impl(h, n, h->d_tickrec, nullptr, nullptr, bf->R_world, bf->foot_pos_abs, bf->contacts, bf->grf, nullptr, bf->iters, bf->status, s, 0, 0, nullptr, &tq);
+    if (a1mpc_status st = solve_device_impl(h, n, h->d_tickrec, nullptr, nullptr, bf->R_world, mpc_foot, mpc_contact, bf->grf, nullptr, bf->iters, bf->status, s, pv_feet ? 12 : 0,
+                                            pv_sched ? 4 : 0, nullptr, &tq);
         st != A1MPC_OK) return st;
     if (!tq.fused) {   // the split pipeline solved this tick (a first tick, a batch beyond the fused kernel's range): N3 as its own launch
         TorqueArgs a;
@@ -2275,6 +2488,14 @@ a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* 
     h->tick_timed = h->timing;
     A1_MARK(h, s);
     return A1MPC_OK;
+}
+a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
+    return control_tick_impl(h, p, nullptr, bf, n, hip_stream);
+}
+// a1mpc_control_tick_device with the preview kernel between the contacts / terrain stage and the MPC launch; {0, 0, *} is a1mpc_control_tick_device
+a1mpc_status a1mpc_control_tick_preview_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
+    if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    return control_tick_impl(h, p, pv, bf, n, hip_stream);
 }
 a1mpc_status a1mpc_last_control_tick_ms(a1mpc_handle h, float* ms_out, int32_t* torques_fused_out) {
     if (!h || !ms_out) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle/out");
@@ -2534,9 +2755,6 @@ a1mpc_status a1mpc_form_qp_batch(a1mpc_handle h, int32_t n, const double* x0, co
     return A1MPC_OK;
 }
 
-static bool strides_ok(int32_t foot_stride, int32_t contact_stride) {
-    return (foot_stride == 0 || foot_stride == 12) && (contact_stride == 0 || contact_stride == 4);
-}
 a1mpc_status a1mpc_solve_batch_strided_device(a1mpc_handle h, int32_t n, const double* d_x0, const double* d_x_ref, const double* d_R_world,
                                               const double* d_foot_abs, int32_t foot_stride, const uint8_t* d_contact, int32_t contact_stride,
                                               const double* d_yaw_A, double* d_grf_body_out, double* d_u_full_out, int32_t* d_iters_out,
@@ -2598,6 +2816,37 @@ a1mpc_status a1mpc_solve_batch_strided(a1mpc_handle h, int32_t n, const double* 
     }
     if (a1mpc_status st = strided_host_submit(h, n, x0, x_ref, R_world, foot_abs, foot_stride, contact, contact_stride, yaw_A, u_full_out != nullptr); st != A1MPC_OK) return st;
     A1_HIP(hipStreamSynchronize(h->stream));
+    host_collect(h, N, 12 * H, grf_body_out, u_full_out, iters_out, status_out);
+    return A1MPC_OK;
+}
+// Tick records + strides, host pointers: staged through device memory at every n (the tick record rides in the x_ref staging buffer like a1mpc_solve_batch_ticks',
+// feet and contacts in the per-step staging of a1mpc_solve_batch_strided), one D2H copy of the packed outputs into the pinned mirror
+a1mpc_status a1mpc_solve_batch_ticks_strided(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs, int32_t foot_stride,
+                                             const uint8_t* contact, int32_t contact_stride, const double* yaw_A, double* grf_body_out, double* u_full_out,
+                                             int32_t* iters_out, int32_t* status_out) {
+    if (!strides_ok(foot_stride, contact_stride)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "foot_stride must be 0 or 12, contact_stride 0 or 4");
+    if (foot_stride == 0 && contact_stride == 0 && !yaw_A)   // a1mpc_solve_batch_ticks itself: same transport, same kernels, same bits
+        return a1mpc_solve_batch_ticks(h, n, tick, R_world, foot_abs, contact, grf_body_out, u_full_out, iters_out, status_out);
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n < 0 || !tick || !R_world || !foot_abs || !contact || !grf_body_out) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
+    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
+    if (h->cfg.horizon < 2) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "tick records need horizon >= 2");
+    if (n == 0) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    if (a1mpc_status st = ensure_step_staging(h); st != A1MPC_OK) return st;
+    const size_t N = n, H = h->cfg.horizon, nfoot = foot_stride ? 12 * H : 12, ncont = contact_stride ? 4 * H : 4;
+    hipStream_t s = h->stream;
+    A1_ORDER(h, s);
+    A1_HIP(hipMemcpyAsync(h->d_xref, tick, N * 22 * sizeof(double), hipMemcpyHostToDevice, s));   // (13H >= 22 doubles per QP for H >= 2)
+    A1_HIP(hipMemcpyAsync(h->d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+    A1_HIP(hipMemcpyAsync(h->d_foot_steps, foot_abs, N * nfoot * sizeof(double), hipMemcpyHostToDevice, s));
+    A1_HIP(hipMemcpyAsync(h->d_contact_steps, contact, N * ncont, hipMemcpyHostToDevice, s));
+    if (yaw_A) A1_HIP(hipMemcpyAsync(h->d_aux, yaw_A, N * sizeof(double), hipMemcpyHostToDevice, s));  // d_aux: n x 6 doubles of balance-QP staging, free here
+    const HostOut o = host_out_layout(h->d_out, N, u_full_out ? 12 * H : 0);
+    if (a1mpc_status st = solve_device_impl(h, n, h->d_xref, nullptr, nullptr, h->d_R, h->d_foot_steps, h->d_contact_steps, o.grf, o.u, o.iters, o.status, s, foot_stride,
+                                            contact_stride, yaw_A ? h->d_aux : nullptr); st != A1MPC_OK) return st;
+    A1_HIP(hipMemcpyAsync(h->h_pin + h->h_pin_in_bytes, h->d_out, o.bytes, hipMemcpyDeviceToHost, s));
+    A1_HIP(hipStreamSynchronize(s));
     host_collect(h, N, 12 * H, grf_body_out, u_full_out, iters_out, status_out);
     return A1MPC_OK;
 }

@@ -45,6 +45,10 @@ class TickParams(C.Structure):  # a1mpc_tick_params
                 ("kp_foot", C.c_double * 3), ("kd_foot", C.c_double * 3), ("km_foot", C.c_double * 3), ("rho_fix", C.c_double * 20), ("rho_opt", C.c_double * 12)]
 
 
+class PreviewConfig(C.Structure):  # a1mpc_preview_config: the gait-aware horizon (contact schedule / foot preview)
+    _fields_ = [("contact_schedule", C.c_int32), ("foot_preview", C.c_int32), ("ticks_per_step", C.c_int32)]
+
+
 TICK_BUFFER_FIELDS = ("joint_pos", "joint_vel", "R_world", "R_z", "root_euler", "root_ang_vel", "imu_acc", "imu_ang_vel", "foot_force", "movement_mode", "mpc_active",
                       "root_lin_vel_d", "root_ang_vel_d", "root_pos_d_z", "gait_counter_speed", "torques_gravity", "gait_counter", "foot_pos_start", "foot_pos_rel_last_time",
                       "foot_pos_target_last_time", "root_euler_d", "joint_torques", "root_pos", "root_lin_vel", "estimated_contacts", "plan_contacts", "contacts", "foot_pos_rel",
@@ -56,7 +60,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_set_timing", "a1mpc_default_tick_params", "a1mpc_control_tick_device", "a1mpc_last_control_tick_ms", "a1mpc_last_stage_ms", "a1mpc_sharded_create", "a1mpc_sharded_solve_batch", "a1mpc_sharded_solve_batch_ticks", "a1mpc_sharded_solve_batch_device", "a1mpc_sharded_solve_batch_ticks_device", "a1mpc_sharded_handle",
+EXPORTS = ["a1mpc_default_preview_config", "a1mpc_horizon_preview_batch", "a1mpc_horizon_preview_batch_device", "a1mpc_solve_batch_ticks_strided", "a1mpc_solve_batch_ticks_strided_device",
+           "a1mpc_control_tick_preview_device", "a1mpc_set_timing", "a1mpc_default_tick_params", "a1mpc_control_tick_device", "a1mpc_last_control_tick_ms", "a1mpc_last_stage_ms", "a1mpc_sharded_create", "a1mpc_sharded_solve_batch", "a1mpc_sharded_solve_batch_ticks", "a1mpc_sharded_solve_batch_device", "a1mpc_sharded_solve_batch_ticks_device", "a1mpc_sharded_handle",
            "a1mpc_sharded_last_transfer", "a1mpc_sharded_info", "a1mpc_sharded_destroy", "a1mpc_terrain_batch", "a1mpc_form_qp_batch", "a1mpc_solve_batch_strided", "a1mpc_solve_batch_strided_device", "a1mpc_update_config", "a1mpc_warm_start", "a1mpc_get_warm_start", "a1mpc_get_workspace_z", "a1mpc_get_workspace_scaling", "a1mpc_last_warm_start_mode", "a1mpc_set_profiling", "a1mpc_last_stage_cycles", "a1mpc_last_tick_stage_cycles", "a1mpc_update_plan_batch_device", "a1mpc_swing_legs_batch_device", "a1mpc_contact_terrain_batch_device", "a1mpc_leg_state_batch_device",
            "a1mpc_ekf_update_batch_device", "a1mpc_joint_torques_batch_device", "a1mpc_ekf_update_batch", "a1mpc_reset_ekf_state", "a1mpc_leg_state_batch", "a1mpc_swing_legs_batch", "a1mpc_default_contact_config", "a1mpc_contact_terrain_batch", "a1mpc_reset_contact_state", "a1mpc_default_gait_config", "a1mpc_update_plan_batch", "a1mpc_joint_torques_batch", "a1mpc_set_schedule", "a1mpc_default_config", "a1mpc_default_balance_config", "a1mpc_create", "a1mpc_destroy", "a1mpc_solve_batch",
            "a1mpc_solve_batch_device", "a1mpc_solve_batch_ticks", "a1mpc_solve_batch_ticks_device", "a1mpc_balance_solve_batch", "a1mpc_reset_warm_start", "a1mpc_last_kernel_ms",
@@ -152,6 +157,16 @@ def load_library(path=None):
         lib.a1mpc_default_tick_params.argtypes = [C.POINTER(TickParams)]; lib.a1mpc_default_tick_params.restype = None
         lib.a1mpc_control_tick_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(TickBuffers), i32, vp]; lib.a1mpc_control_tick_device.restype = C.c_int
         lib.a1mpc_last_control_tick_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]; lib.a1mpc_last_control_tick_ms.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_preview_device"):   # (the gait-aware horizon; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_default_preview_config.argtypes = [C.POINTER(PreviewConfig)]; lib.a1mpc_default_preview_config.restype = None
+        lib.a1mpc_horizon_preview_batch.argtypes = [vp, C.POINTER(PreviewConfig), C.POINTER(GaitConfig), i32, u8p, dp, dp, u8p, dp, dp, dp, u8p, dp]
+        lib.a1mpc_horizon_preview_batch.restype = C.c_int
+        lib.a1mpc_horizon_preview_batch_device.argtypes = [vp, C.POINTER(PreviewConfig), C.POINTER(GaitConfig), i32] + [vpp] * 9 + [vpp]
+        lib.a1mpc_horizon_preview_batch_device.restype = C.c_int
+        lib.a1mpc_solve_batch_ticks_strided.argtypes = [vp, i32, dp, dp, dp, i32, u8p, i32, dp, dp, dp, i32p, i32p]; lib.a1mpc_solve_batch_ticks_strided.restype = C.c_int
+        lib.a1mpc_solve_batch_ticks_strided_device.argtypes = [vp, i32] + [vpp] * 3 + [i32, vpp, i32] + [vpp] * 5 + [vpp]; lib.a1mpc_solve_batch_ticks_strided_device.restype = C.c_int
+        lib.a1mpc_control_tick_preview_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(PreviewConfig), C.POINTER(TickBuffers), i32, vp]
+        lib.a1mpc_control_tick_preview_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_last_tick_stage_cycles"):  # (round 5; an older build bound by hand for an A/B may lack it)
         lib.a1mpc_last_tick_stage_cycles.argtypes = [vp, dp, C.POINTER(C.c_int32)]; lib.a1mpc_last_tick_stage_cycles.restype = C.c_int
     lib.a1mpc_set_schedule.argtypes = [vp, i32]; lib.a1mpc_set_schedule.restype = C.c_int
@@ -313,6 +328,51 @@ class Engine:
     def control_tick_device(self, params, buffers, n, stream=None):
         """a1mpc_control_tick_device: one whole control tick of n robots (device pointers in a TickBuffers), asynchronous on `stream`"""
         _check(self.lib, self.lib.a1mpc_control_tick_device(self._h, C.byref(params), C.byref(buffers), int(n), C.c_void_p(stream) if stream else None), "a1mpc_control_tick_device")
+
+    def control_tick_preview_device(self, params, preview, buffers, n, stream=None):
+        """a1mpc_control_tick_preview_device: the control tick with the gait-aware horizon (a PreviewConfig) between the contacts stage and the MPC launch"""
+        _check(self.lib, self.lib.a1mpc_control_tick_preview_device(self._h, C.byref(params), C.byref(preview), C.byref(buffers), int(n), C.c_void_p(stream) if stream else None),
+               "a1mpc_control_tick_preview_device")
+
+    def preview_config(self, **fields):
+        """a1mpc_default_preview_config ({1, 0, 1}) with `fields` (contact_schedule, foot_preview, ticks_per_step) overridden"""
+        pv = PreviewConfig(); self.lib.a1mpc_default_preview_config(C.byref(pv))
+        for k, v in fields.items():
+            if not hasattr(pv, k):
+                raise KeyError(k)
+            setattr(pv, k, int(v))
+        return pv
+
+    # ---- the gait-aware horizon: contact schedule (update_plan's counter rule run forward) and per-step feet, the inputs of solve_strided / solve_ticks_strided ----
+    def horizon_preview(self, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs=None, R=None, root_lin_vel_d=None, preview=None, gait=None,
+                        want_schedule=True):
+        """dict(contact_sched (n, 4 H) uint8 or None, foot_steps (n, 12 H) or None): a1mpc_horizon_preview_batch.  The feet are produced when preview.foot_preview is 1 or 2."""
+        if gait is None:
+            gait = GaitConfig(); self.lib.a1mpc_default_gait_config(C.byref(gait))
+        pv = self.preview_config() if preview is None else preview
+        h = self.horizon
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(-1, 4); n = ct.shape[0]
+        mm = np.ascontiguousarray(movement_mode, dtype=np.uint8).reshape(n)
+        gc = _f64(gait_counter, (n, 4)); spd = _f64(gait_counter_speed, (n, 4))
+        fp = None if foot_pos_abs is None else _f64(foot_pos_abs, (n, 12)); Rw = None if R is None else _f64(R, (n, 9)); vd = None if root_lin_vel_d is None else _f64(root_lin_vel_d, (n, 3))
+        sched = np.zeros((n, 4 * h), np.uint8) if want_schedule else None
+        feet = np.zeros((n, 12 * h)) if pv.foot_preview != 0 else None
+        rc = self.lib.a1mpc_horizon_preview_batch(self._h, C.byref(pv), C.byref(gait), n, _u8p(mm), _dp(gc), _dp(spd), _u8p(ct), _dp(fp), _dp(Rw), _dp(vd), _u8p(sched), _dp(feet))
+        _check(self.lib, rc, "a1mpc_horizon_preview_batch")
+        return dict(contact_sched=sched, foot_steps=feet)
+
+    # ---- N1 + the general interface: tick records with per-step feet / a contact schedule / an A_c yaw of its own ----
+    def solve_ticks_strided(self, tick, R, foot, foot_stride, contact, contact_stride, want_u=False, yaw_A=None):
+        h = self.horizon
+        tick = _f64(tick, (-1, 22)); n = tick.shape[0]
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12 * h if foot_stride else 12))
+        contact = np.ascontiguousarray(contact, dtype=np.uint8).reshape(n, 4 * h if contact_stride else 4)
+        grf = np.zeros((n, 12)); u = np.zeros((n, NU * h)) if want_u else None
+        iters = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
+        rc = self.lib.a1mpc_solve_batch_ticks_strided(self._h, n, _dp(tick), _dp(R), _dp(foot), int(foot_stride), _u8p(contact), int(contact_stride),
+                                                      None if yaw_A is None else _dp(np.ascontiguousarray(yaw_A, dtype=np.float64)), _dp(grf), _dp(u), _ip(iters), _ip(status))
+        _check(self.lib, rc, "a1mpc_solve_batch_ticks_strided")
+        return dict(grf=grf, u=u, iters=iters, status=status)
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

@@ -410,6 +410,82 @@ a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* 
 a1mpc_status a1mpc_last_control_tick_ms(a1mpc_handle h, float* ms_out, int32_t* torques_fused_out);
 
 /*
+ * Gait-aware horizon: the device-side PRODUCER of the two inputs a1mpc_solve_batch_strided takes beyond the reference controller's -- a contact schedule over the
+ * horizon and per-step feet -- from the state a control tick already holds on the device (gait counters, contacts, feet, the velocity command).
+ * NOT the reference controller's behaviour unless switched off: calculate_qp_mats broadcasts the current contacts[] over all H steps (S/ConvexMpc.cpp:228-245) and
+ * compute_grf passes the current feet at every step (S/A1RobotControl.cpp:498-514; the per-step shift is commented out there, :496,:504-507).  What IS the
+ * reference's: the counter rule that is run forward (update_plan, S/A1RobotControl.cpp:156-164), the per-step interface that takes the result (B_mat_d_list,
+ * S/ConvexMpc.h:74) and the foot recurrence (S/test/test_mpc.cpp:105-122, S/A1RobotControl.cpp:504-507).
+ *   contact_schedule  0: no schedule is produced; the solve broadcasts contacts[] (the reference).
+ *                     1: step 0 = the robot's ACTUAL contacts[] (planned or early contact, S/A1RobotControl.cpp:271 -- the value the reference broadcasts); step t >= 1 =
+ *                        update_plan's rule run forward from the CURRENT gait_counter (already advanced by this tick's update_plan): t * ticks_per_step times
+ *                        c = fmod(c + speed, counter_per_gait), then contact = (c <= counter_per_swing) (:158-164).  The update is iterated, not a closed form, so step t
+ *                        is bit for bit the plan_contacts update_plan itself produces t * ticks_per_step ticks later at constant speed.  movement_mode == 0: every
+ *                        step is 1 (:150-153).  Early contacts and the foot-force test (:256-282) are not predicted: beyond step 0 the schedule is the PLAN.
+ *   foot_preview      0: no per-step feet are produced; the solve uses the current feet at every step (the reference controller).
+ *                     1: the reference's lines as written: f_0 = foot_pos_abs, f_(t+1) = f_t - root_lin_vel_d * dt with root_lin_vel_d the BODY-frame command exactly
+ *                        as S/test/test_mpc.cpp:112-115 and S/A1RobotControl.cpp:504-507 have it, dt = the handle's cfg.dt.
+ *                     2: the same recurrence with R_world * root_lin_vel_d, the world-frame command root_lin_vel_d_world of S/A1RobotControl.cpp:470 -- foot_pos_abs is
+ *                        world-aligned, so this is the physically consistent variant (not in the reference).
+ *                     The product is rounded first and then subtracted (no FMA contraction): bit-identical to the C++ loop.
+ *   ticks_per_step    1..64: control ticks per horizon step (mpc_dt / control period).  The reference runs 1: mpc_dt equals the control period (S/A1RobotControl.cpp:462).
+ * a1mpc_default_preview_config: {1, 0, 1}.
+ */
+typedef struct a1mpc_preview_config {
+    int32_t contact_schedule;  /* 0: broadcast contacts (the reference), 1: gait-predicted schedule */
+    int32_t foot_preview;      /* 0 / 1 / 2 as above */
+    int32_t ticks_per_step;    /* 1..64 */
+} a1mpc_preview_config;
+void a1mpc_default_preview_config(a1mpc_preview_config* cfg);
+/*
+ * The preview on its own, n robots, horizon H = the handle's (>= 2).  Of `gait` only counter_per_gait (> 0) and counter_per_swing are read.
+ *   movement_mode n, gait_counter n x 4, gait_counter_speed n x 4, contacts n x 4, foot_pos_abs n x 12 (3x4 column-major), R_world n x 9 (row-major; read by
+ *   foot_preview 2 only, may be NULL otherwise), root_lin_vel_d n x 3 (body frame)
+ * out: contact_sched_out n x 4H bytes, step t of robot i at [(i*H + t)*4]; foot_steps_out n x 12H doubles, step t of robot i at [(i*H + t)*12] -- the layouts
+ * a1mpc_solve_batch_strided takes with contact_stride = 4 / foot_stride = 12.  Either may be NULL (not produced).  With contact_schedule 0 a schedule that is asked for is
+ * contacts[] at every step, the reference's broadcast written out (same solve as contact_stride = 0); the feet need foot_preview 1 or 2.  The inputs of an output
+ * that is not produced may be NULL (the schedule reads movement_mode, gait_counter, gait_counter_speed, contacts; the feet foot_pos_abs, root_lin_vel_d, R_world).  Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field): a null config, ticks_per_step outside 1..64, foot_preview outside
+ * 0..2, contact_schedule outside 0..1, horizon 1, counter_per_gait <= 0, foot_steps_out with foot_preview 0.
+ * Host pointers; a1mpc_horizon_preview_batch_device: device pointers, asynchronous on hip_stream (NULL = the handle's).
+ */
+a1mpc_status a1mpc_horizon_preview_batch(a1mpc_handle h, const a1mpc_preview_config* cfg, const a1mpc_gait_config* gait, int32_t n,
+                                         const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts,
+                                         const double* foot_pos_abs, const double* R_world, const double* root_lin_vel_d, uint8_t* contact_sched_out,
+                                         double* foot_steps_out);
+a1mpc_status a1mpc_horizon_preview_batch_device(a1mpc_handle h, const a1mpc_preview_config* cfg, const a1mpc_gait_config* gait, int32_t n,
+                                                const uint8_t* d_movement_mode, const double* d_gait_counter, const double* d_gait_counter_speed,
+                                                const uint8_t* d_contacts, const double* d_foot_pos_abs, const double* d_R_world, const double* d_root_lin_vel_d,
+                                                uint8_t* d_contact_sched_out, double* d_foot_steps_out, void* hip_stream);
+/*
+ * Tick records (a1mpc_solve_batch_ticks: x0 / x_ref built on the device, S/A1RobotControl.cpp:452-488) joined with the strides of a1mpc_solve_batch_strided.
+ * (foot_stride, contact_stride, yaw_A) = (0, 0, NULL) IS a1mpc_solve_batch_ticks(_device): same kernels, same bits.  (0, 4, NULL) runs the fast kernels at their speed
+ * (contacts only change bounds and equality rows).  Per-step feet and / or a yaw_A run the general kernels, whose set-up builds x0 / x_ref from the record exactly as
+ * the fast path's does; with yaw_A = NULL the A_c yaw is the record's root_euler[2] (= mpc_states[2], S/A1RobotControl.cpp:452,492).  Same iterates as
+ * a1mpc_solve_batch_strided on the explicit x0 / x_ref up to the rounding of x_ref (base + (slope * dt) * (i + 1) here as in compute_grf).  All warm-start modes as on
+ * the underlying entries.  The host-pointer entry stages through device memory at every n (no pinned small-batch transport).  Horizon >= 2.
+ */
+a1mpc_status a1mpc_solve_batch_ticks_strided(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs, int32_t foot_stride,
+                                             const uint8_t* contact, int32_t contact_stride, const double* yaw_A, double* grf_body_out, double* u_full_out,
+                                             int32_t* iters_out, int32_t* status_out);
+a1mpc_status a1mpc_solve_batch_ticks_strided_device(a1mpc_handle h, int32_t n, const double* d_tick, const double* d_R_world, const double* d_foot_abs,
+                                                    int32_t foot_stride, const uint8_t* d_contact, int32_t contact_stride, const double* d_yaw_A,
+                                                    double* d_grf_body_out, double* d_u_full_out, int32_t* d_iters_out, int32_t* d_status_out, void* hip_stream);
+/*
+ * a1mpc_control_tick_device with the preview between the contacts / terrain stage and the MPC launch: the chain of a1mpc_control_tick_device in which
+ * a1mpc_horizon_preview_batch_device (schedule and / or feet into handle-owned device buffers, allocated once) + a1mpc_solve_batch_ticks_strided_device +
+ * a1mpc_joint_torques_batch_device replace the ticks solve -- bit-identical to chaining those entries by hand.
+ *   {0, 0, *}                      IS a1mpc_control_tick_device: same launches (no preview kernel), same bits, same torques_fused.
+ *   contact_schedule 1, feet 0     the tick stays on the fast kernels; compute_joint_torques (N3) stays in the MPC kernel's output stage wherever it is today -- that
+ *                                  stage reads step 0 of the schedule, the actual contacts[], so the torques keep their meaning.
+ *   foot_preview 1 / 2             the general kernels solve the tick (1.7-2.5x the fast path's first solves, see a1mpc_solve_batch_strided); they have no torque stage, so
+ *                                  the joint torques are a1mpc_torque_kernel as a launch of its own and a1mpc_last_control_tick_ms reports torques_fused = 0.
+ * cfg.warm_start 0 / 1 / 2 behave as on the underlying solve entries (a1mpc_last_warm_start_mode stays truthful).  a1mpc_last_control_tick_ms reports this tick too.
+ * Validation as a1mpc_horizon_preview_batch (params->gait.counter_per_gait <= 0 is refused whenever a preview is on).
+ */
+a1mpc_status a1mpc_control_tick_preview_device(a1mpc_handle h, const a1mpc_tick_params* params, const a1mpc_preview_config* preview,
+                                               const a1mpc_tick_buffers* buffers, int32_t n, void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
