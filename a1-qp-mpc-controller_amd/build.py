@@ -79,9 +79,8 @@ def needs_build():
 def unit_key(unit):
     """what an object file is the compilation of: the unit, every header it can see, the flags and the compiler"""
     h = hashlib.sha256()
-    deps = [unit] + (HEADERS if unit == MAIN_UNIT else HEADERS)   # (the C ABI unit includes a1mpc_common.hpp -> a1mpc_solver.hpp too, but not a1mpc_kernels.hpp)
-    if unit == MAIN_UNIT:
-        deps = [d for d in deps if d != "a1mpc_kernels.hpp"]
+    # every header, except that the C ABI unit does not see a1mpc_kernels.hpp (it reaches a1mpc_solver.hpp through a1mpc_common.hpp)
+    deps = [unit] + [d for d in HEADERS if not (unit == MAIN_UNIT and d == "a1mpc_kernels.hpp")]
     for d in deps:
         h.update(open(os.path.join(CSRC, d), "rb").read())
     h.update(open(_public_header(), "rb").read())

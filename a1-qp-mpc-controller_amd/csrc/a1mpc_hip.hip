@@ -598,7 +598,7 @@ struct a1mpc_handle_s {
     uint32_t* d_pv_sched = nullptr; // a1mpc_control_tick_preview_device: n x H words, the horizon's contact schedule (allocated on first use)
     double* d_pv_foot = nullptr;    // ... and n x 12H per-step feet (allocated on first use)
     int32_t ekf_ready_n = 0;        // robots 0 .. ekf_ready_n - 1 have had their filter initialised (the init kernel is not launched for them again)
-    // staging of the element-wise entry points (N2a, N2b, N3), allocated on first use: 64 / 96 doubles and 16 bytes per robot
+    // staging of the host-pointer entries of the caller-side stages, allocated on first use (ensure_aux; handed out by Staging)
     double *d_aux_in = nullptr, *d_aux_out = nullptr;
     uint8_t* d_aux_u8 = nullptr;
     int32_t hint_n = 0;  // batch size the order was built for (0 = none)
@@ -626,6 +626,8 @@ static a1mpc_status mark_launched(a1mpc_handle h, hipStream_t s) {
 }
 #define A1_ORDER(h, s) do { if (a1mpc_status so_ = order_streams(h, s); so_ != A1MPC_OK) return so_; } while (0)
 #define A1_MARK(h, s) do { if (a1mpc_status sm_ = mark_launched(h, s); sm_ != A1MPC_OK) return sm_; } while (0)
+// grid of the kernels that run one lane per (robot, leg) in workgroups of 256
+static dim3 leg_lane_grid(int32_t n) { return dim3(static_cast<unsigned>((static_cast<size_t>(n) * 4 + 255) / 256)); }
 
 extern "C" {
 
@@ -874,24 +876,110 @@ static a1mpc_status ensure_contact_state(a1mpc_handle h, hipStream_t s) {
     A1_HIP(hipMemsetAsync(h->d_ct_state, 0, static_cast<size_t>(h->max_batch) * kCtBytesPerRobot, s));
     return A1MPC_OK;
 }
-static void contact_state_pointers(a1mpc_handle h, ContactArgs& a) {
+// Every field of ContactArgs, for its four users.  As filled here: root_pos_z / pitch_d are arrays of their own (strides 1), no tick record is packed and
+// foot_pos_recent_contact is the handle's; the control tick and a1mpc_terrain_batch set the few fields they differ in on the result.
+static ContactArgs make_contact_args(a1mpc_handle h, const a1mpc_contact_config& cfg, int32_t n, const double* gait_counter, const uint8_t* plan_contacts,
+                                     const double* foot_force, const double* foot_pos_abs, const double* root_pos_z, double* pitch_d, uint8_t* contacts, double* recent_out,
+                                     double* terrain_out) {
+    ContactArgs a;
+    a.n = n; a.counter_per_swing = cfg.counter_per_swing; a.foot_force_low = cfg.foot_force_low; a.use_terrain_adapt = cfg.use_terrain_adapt;
     a.rec = reinterpret_cast<CtRecord*>(h->d_ct_state);
     a.leg_ring = reinterpret_cast<double*>(a.rec + h->max_batch);
     a.terrain_ring = a.leg_ring + static_cast<size_t>(h->max_batch) * kCtLegRing;
     a.stride = h->max_batch;
+    a.gait_counter = gait_counter; a.foot_force = foot_force; a.foot_pos_abs = foot_pos_abs; a.root_pos_z = root_pos_z; a.plan_contacts = plan_contacts;
+    a.pitch_d = pitch_d; a.z_stride = 1; a.pitch_stride = 1;
+    a.pk_euler = a.pk_pos = a.pk_ang_vel = a.pk_lin_vel = a.pk_euler_d = a.pk_lin_vel_d = a.pk_ang_vel_d = a.pk_pos_d_z = nullptr; a.pk_tick = nullptr;
+    a.contacts = contacts; a.recent_out = recent_out; a.terrain_out = terrain_out; a.recent_in = nullptr;
+    return a;
 }
 static void launch_contact_terrain(const ContactArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(a1mpc_contact_terrain_kernel, dim3(static_cast<unsigned>((a.n + 63) / 64)), dim3(64), 0, s, a);
 }
 
+// ---- what the entry points of the caller-side stages share.  A stage has a launcher (launch_<stage>: scalars and DEVICE pointers in, the args struct filled and the
+// kernel launched on a stream the caller has ordered) and two entries around it: the device-pointer one is the macros below and the launcher, the host-pointer
+// one also stages the caller's arrays through the handle's staging buffers (Staging) on the handle's stream.
+//   A1_STAGE_BEGIN   every refusal, all before the first HIP call; then A1_STAGE_DEVICE (on its own where an entry has refusals of its own in front): the device and
+//                    the stream `s` (hip_stream, or null = the handle's), ordered behind the handle's previous launch -- once: the launchers do not order again
+//   A1_STAGE_LAUNCH  the launch between the timing events, its status, and the mark that the next call's ordering waits for
+static hipStream_t stream_or_own(a1mpc_handle h, void* hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream; }
+#define A1_STAGE_DEVICE(hip_stream)                                                                           \
+    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");      \
+    if (n == 0) return A1MPC_OK;                                                                             \
+    A1_HIP(hipSetDevice(h->device));                                                                         \
+    hipStream_t s = stream_or_own(h, hip_stream);                                                            \
+    A1_ORDER(h, s)
+#define A1_STAGE_BEGIN(ok, what, hip_stream)                                            \
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");                      \
+    if (n < 0 || !(ok)) return fail(A1MPC_ERR_INVALID_ARGUMENT, what);                   \
+    A1_STAGE_DEVICE(hip_stream)
+#define A1_STAGE_LAUNCH(...)                                  \
+    do {                                                      \
+        if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));     \
+        __VA_ARGS__;                                          \
+        A1_HIP(hipGetLastError());                            \
+        if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));     \
+        h->timed = h->timing; A1_MARK(h, s);                  \
+    } while (0)
+
+// The handle's staging for the host-pointer entries, allocated on first use.  Per robot: kAuxIn + kAuxOut doubles in two blocks, and kAuxU8 bytes handed out in
+// slices of kAuxU8Slice (every byte array starts 8-byte aligned whatever the batch size)
+constexpr size_t kAuxIn = 64, kAuxOut = 96, kAuxU8 = 16, kAuxU8Slice = 8;
 static a1mpc_status ensure_aux(a1mpc_handle h) {
     if (h->d_aux_in) return A1MPC_OK;
     const size_t n = static_cast<size_t>(h->max_batch);
-    A1_HIP(hipMalloc(&h->d_aux_in, n * 64 * sizeof(double)));
-    A1_HIP(hipMalloc(&h->d_aux_out, n * 96 * sizeof(double)));
-    A1_HIP(hipMalloc(&h->d_aux_u8, n * 16));
+    A1_HIP(hipMalloc(&h->d_aux_in, n * kAuxIn * sizeof(double)));
+    A1_HIP(hipMalloc(&h->d_aux_out, n * kAuxOut * sizeof(double)));
+    A1_HIP(hipMalloc(&h->d_aux_u8, n * kAuxU8));
     return A1MPC_OK;
 }
+// One host-pointer call's view of that staging: consecutive per-robot slices (doubles from d_aux_in while it has room, then from d_aux_out), the inbound copies issued
+// as the slices are handed out, the outbound ones remembered in the order they are asked for.  A slice the buffers do not hold is REFUSED: the first refusal or HIP
+// error sticks in `st` and every later request returns null without touching the device, so an entry checks st once, before it launches.
+extern "C++" {   // (member templates; this section sits inside the ABI's extern "C" block)
+struct Staging {
+    struct Back { void* host; const void* dev; size_t bytes; };
+    a1mpc_handle h; size_t N; hipStream_t s;
+    a1mpc_status st;
+    size_t used_in = 0, used_out = 0, used_u8 = 0;   // per robot
+    Back backs[8]; int n_backs = 0;
+    Staging(a1mpc_handle h_, int32_t n, hipStream_t s_) : h(h_), N(static_cast<size_t>(n)), s(s_), st(ensure_aux(h_)) {}
+    void hip(hipError_t e, const char* what) { if (e != hipSuccess) st = fail(A1MPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+    void refuse(const char* what) { st = fail(A1MPC_ERR_INVALID_ARGUMENT, std::string("internal: ") + what + " beyond what the handle's staging holds"); }
+    void take(double*& d, size_t per_robot) {
+        if (used_in + per_robot <= kAuxIn) { d = h->d_aux_in + used_in * N; used_in += per_robot; }
+        else if (used_out + per_robot <= kAuxOut) { d = h->d_aux_out + used_out * N; used_out += per_robot; }
+        else refuse("a slice of doubles");
+    }
+    void take(uint8_t*& d, size_t per_robot) {
+        if (per_robot <= kAuxU8Slice && used_u8 + kAuxU8Slice <= kAuxU8) { d = h->d_aux_u8 + used_u8 * N; used_u8 += kAuxU8Slice; }
+        else refuse("a slice of bytes");
+    }
+    template <class T> T* slice(size_t per_robot) { T* d = nullptr; if (st == A1MPC_OK) take(d, per_robot); return d; }
+    // an input: the slice, filled from `host` (null host: the slice alone -- an input the call does not use)
+    template <class T> T* in(const T* host, size_t per_robot) {
+        T* d = slice<T>(per_robot);
+        if (d && host) hip(hipMemcpyAsync(d, host, N * per_robot * sizeof(T), hipMemcpyHostToDevice, s), "hipMemcpyAsync (staging, host to device)");
+        return d;
+    }
+    // `dev` (per_robot elements per robot) goes back to `host` in finish(); a null host is an output the caller does not want: nothing is copied
+    template <class T> void back(T* host, const T* dev, size_t per_robot) {
+        if (!host || st != A1MPC_OK) return;
+        if (n_backs == static_cast<int>(sizeof backs / sizeof backs[0])) return refuse("an output");
+        backs[n_backs++] = Back{host, dev, N * per_robot * sizeof(T)};
+    }
+    // an output: its slice, or null for a null host (the kernels skip a null optional output)
+    template <class T> T* out(T* host, size_t per_robot) { if (!host) return nullptr; T* d = slice<T>(per_robot); back(host, d, per_robot); return d; }
+    template <class T> T* inout(T* host, size_t per_robot) { T* d = in(host, per_robot); back(host, d, per_robot); return d; }
+    a1mpc_status finish() {   // the outbound copies, then the call's one synchronisation
+        for (int k = 0; k < n_backs; ++k) A1_HIP(hipMemcpyAsync(backs[k].host, backs[k].dev, backs[k].bytes, hipMemcpyDeviceToHost, s));
+        A1_HIP(hipStreamSynchronize(s));
+        return A1MPC_OK;
+    }
+};
+}  // extern "C++"
+#define A1_STAGED(sg) do { if ((sg).st != A1MPC_OK) return (sg).st; } while (0)
 
 void a1mpc_default_contact_config(a1mpc_contact_config* c) {
     if (!c) return;
@@ -910,44 +998,39 @@ a1mpc_status a1mpc_contact_terrain_batch(a1mpc_handle h, const a1mpc_contact_con
                                          const uint8_t* plan_contacts, const double* foot_force, const double* foot_pos_abs,
                                          const double* root_pos_z, double* root_euler_d_pitch, uint8_t* contacts_out,
                                          double* foot_pos_recent_contact_out, double* terrain_angle_out) {
-    if (!h || !cfg) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle/config");
-    if (n < 0 || !gait_counter || !plan_contacts || !foot_force || !foot_pos_abs || !root_pos_z || !root_euler_d_pitch || !contacts_out ||
-        !foot_pos_recent_contact_out || !terrain_angle_out)
-        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
+    A1_STAGE_BEGIN(cfg && gait_counter && plan_contacts && foot_force && foot_pos_abs && root_pos_z && root_euler_d_pitch && contacts_out &&
+                   foot_pos_recent_contact_out && terrain_angle_out, "null config or input/output pointer", nullptr);
+    Staging sg(h, n, s);
     if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
-    // staging: in [gc 4 | ff 4 | foot 12 | z 1 | pitch 1], out [recent 12 | terrain 1]
-    double *d_gc = h->d_aux_in, *d_ff = d_gc + 4 * N, *d_fp = d_ff + 4 * N, *d_z = d_fp + 12 * N, *d_pd = d_z + N;
-    double *d_rec = h->d_aux_out, *d_ta = d_rec + 12 * N;
-    uint8_t *d_pc = h->d_aux_u8, *d_ct = h->d_aux_u8 + 8 * N;
-    A1_HIP(hipMemcpyAsync(d_gc, gait_counter, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_ff, foot_force, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_fp, foot_pos_abs, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_z, root_pos_z, N * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_pd, root_euler_d_pitch, N * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_pc, plan_contacts, N * 4, hipMemcpyHostToDevice, s));
-    ContactArgs a;
-    a.recent_in = nullptr; a.z_stride = 1; a.pitch_stride = 1; a.pk_tick = nullptr;
-    a.n = n; a.counter_per_swing = cfg->counter_per_swing; a.foot_force_low = cfg->foot_force_low; a.use_terrain_adapt = cfg->use_terrain_adapt;
-    contact_state_pointers(h, a); a.gait_counter = d_gc; a.foot_force = d_ff; a.foot_pos_abs = d_fp; a.root_pos_z = d_z; a.plan_contacts = d_pc;
-    a.pitch_d = d_pd; a.contacts = d_ct; a.recent_out = d_rec; a.terrain_out = d_ta;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
+    const double *d_gc = sg.in(gait_counter, 4), *d_ff = sg.in(foot_force, 4), *d_fp = sg.in(foot_pos_abs, 12), *d_z = sg.in(root_pos_z, 1);
+    double* d_pd = sg.in(root_euler_d_pitch, 1);
+    const uint8_t* d_pc = sg.in(plan_contacts, 4);
+    uint8_t* d_ct = sg.out(contacts_out, 4);
+    double *d_rec = sg.out(foot_pos_recent_contact_out, 12), *d_ta = sg.out(terrain_angle_out, 1);
+    sg.back(root_euler_d_pitch, d_pd, 1);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_contact_terrain(make_contact_args(h, *cfg, n, d_gc, d_pc, d_ff, d_fp, d_z, d_pd, d_ct, d_rec, d_ta), s));
+    return sg.finish();
+}
+// the terrain block of compute_grf alone (S/A1RobotControl.cpp:335-376 + compute_walking_surface :566-582): foot_pos_recent_contact comes from the caller's
+// A1CtrlStates (the reference fills it in generate_swing_legs_ctrl); the terrain-angle filter of every robot lives in the handle.  Not timed (ev0 / ev1 stay the
+// previous call's)
+a1mpc_status a1mpc_terrain_batch(a1mpc_handle h, int32_t use_terrain_adapt, int32_t n, const double* foot_pos_recent_contact, const double* root_pos_z,
+                                 double* root_euler_d_pitch, double* terrain_angle_out) {
+    A1_STAGE_BEGIN(foot_pos_recent_contact && root_pos_z && root_euler_d_pitch && terrain_angle_out, "null input/output pointer", nullptr);
+    Staging sg(h, n, s);
+    if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
+    const double *d_rec = sg.in(foot_pos_recent_contact, 12), *d_z = sg.in(root_pos_z, 1);
+    double* d_pd = sg.in(root_euler_d_pitch, 1);
+    double* d_ta = sg.out(terrain_angle_out, 1);
+    sg.back(root_euler_d_pitch, d_pd, 1);
+    A1_STAGED(sg);
+    ContactArgs a = make_contact_args(h, a1mpc_contact_config{0.0, 0.0, use_terrain_adapt}, n, nullptr, nullptr, nullptr, nullptr, d_z, d_pd, nullptr, nullptr, d_ta);
+    a.recent_in = d_rec;
     launch_contact_terrain(a, s);
     A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(contacts_out, d_ct, N * 4, hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(foot_pos_recent_contact_out, d_rec, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(terrain_angle_out, d_ta, N * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(root_euler_d_pitch, d_pd, N * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
-    return A1MPC_OK;
+    A1_MARK(h, s);
+    return sg.finish();
 }
 
 // ---- N4a: swing-leg targets + foot PD force (S/A1RobotControl.cpp:204-254, Bezier: S/utils/Utils.cpp:64-104), one lane per (robot, leg) ------
@@ -1040,49 +1123,31 @@ __global__ __launch_bounds__(256) void a1mpc_plan_swing_kernel(const PlanArgs pa
     ws.flush3(kin, cur, cur, sa.kin_out, sa.cur_out, nullptr);
 }
 
+static SwingArgs make_swing_args(int32_t n, double counter_per_swing, double dt, const double* kp_foot, const double* kd_foot, const double* R_z, const double* foot_pos_abs,
+                                 const double* gait_counter, const double* foot_pos_target_rel, double* foot_pos_start, double* foot_pos_rel_last_time,
+                                 double* foot_pos_target_last_time, double* foot_pos_cur_out, double* foot_forces_kin_out) {
+    SwingArgs a;
+    a.n = n; a.counter_per_swing = counter_per_swing; a.dt = dt;
+    for (int k = 0; k < 3; ++k) { a.kp[k] = kp_foot[k]; a.kd[k] = kd_foot[k]; }
+    a.Rz = R_z; a.foot_pos_abs = foot_pos_abs; a.gait_counter = gait_counter; a.target_rel = foot_pos_target_rel; a.start = foot_pos_start;
+    a.rel_last = foot_pos_rel_last_time; a.target_last = foot_pos_target_last_time; a.cur_out = foot_pos_cur_out; a.kin_out = foot_forces_kin_out;
+    return a;
+}
+static void launch_swing(const SwingArgs& a, hipStream_t s) { hipLaunchKernelGGL(a1mpc_swing_kernel, leg_lane_grid(a.n), dim3(256), 0, s, a); }
+
 a1mpc_status a1mpc_swing_legs_batch(a1mpc_handle h, int32_t n, double counter_per_swing, double dt, const double* R_z,
                                     const double* foot_pos_abs, const double* gait_counter, const double* foot_pos_target_rel,
                                     const double* kp_foot, const double* kd_foot, double* foot_pos_start, double* foot_pos_rel_last_time,
                                     double* foot_pos_target_last_time, double* foot_pos_cur_out, double* foot_forces_kin_out) {
-    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || !R_z || !foot_pos_abs || !gait_counter || !foot_pos_target_rel || !kp_foot || !kd_foot || !foot_pos_start || !foot_pos_rel_last_time ||
-        !foot_pos_target_last_time || !foot_pos_cur_out || !foot_forces_kin_out || !(dt > 0))
-        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer or dt <= 0");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    // staging: in [Rz 9 | foot 12 | gc 4 | target_rel 12] = 37, in/out + out [start 12 | rel_last 12 | target_last 12] (aux_in tail, 36) and [cur 12 | kin 12]
-    double *d_Rz = h->d_aux_in, *d_fa = d_Rz + 9 * N, *d_gc = d_fa + 12 * N, *d_tr = d_gc + 4 * N;
-    double *d_st = h->d_aux_out, *d_rl = d_st + 12 * N, *d_tl = d_rl + 12 * N;
-    double *d_cur = d_tr + 12 * N, *d_kin = d_cur + 12 * N;   // aux_in has 64 doubles per robot: 37 + 24 = 61
-    A1_HIP(hipMemcpyAsync(d_Rz, R_z, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_fa, foot_pos_abs, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_gc, gait_counter, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_tr, foot_pos_target_rel, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_st, foot_pos_start, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_rl, foot_pos_rel_last_time, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_tl, foot_pos_target_last_time, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    SwingArgs a;
-    a.n = n; a.counter_per_swing = counter_per_swing; a.dt = dt;
-    for (int k = 0; k < 3; ++k) { a.kp[k] = kp_foot[k]; a.kd[k] = kd_foot[k]; }
-    a.Rz = d_Rz; a.foot_pos_abs = d_fa; a.gait_counter = d_gc; a.target_rel = d_tr; a.start = d_st; a.rel_last = d_rl; a.target_last = d_tl;
-    a.cur_out = d_cur; a.kin_out = d_kin;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_swing_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(foot_pos_start, d_st, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(foot_pos_rel_last_time, d_rl, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(foot_pos_target_last_time, d_tl, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(foot_pos_cur_out, d_cur, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(foot_forces_kin_out, d_kin, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
-    return A1MPC_OK;
+    A1_STAGE_BEGIN(R_z && foot_pos_abs && gait_counter && foot_pos_target_rel && kp_foot && kd_foot && foot_pos_start && foot_pos_rel_last_time &&
+                   foot_pos_target_last_time && foot_pos_cur_out && foot_forces_kin_out && dt > 0, "null input/output pointer or dt <= 0", nullptr);
+    Staging sg(h, n, s);
+    const double *d_Rz = sg.in(R_z, 9), *d_fa = sg.in(foot_pos_abs, 12), *d_gc = sg.in(gait_counter, 4), *d_tr = sg.in(foot_pos_target_rel, 12);
+    double *d_st = sg.inout(foot_pos_start, 12), *d_rl = sg.inout(foot_pos_rel_last_time, 12), *d_tl = sg.inout(foot_pos_target_last_time, 12);
+    double *d_cur = sg.out(foot_pos_cur_out, 12), *d_kin = sg.out(foot_forces_kin_out, 12);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_swing(make_swing_args(n, counter_per_swing, dt, kp_foot, kd_foot, d_Rz, d_fa, d_gc, d_tr, d_st, d_rl, d_tl, d_cur, d_kin), s));
+    return sg.finish();
 }
 
 // ---- N4b: leg kinematics (S/GazeboA1ROS.cpp:264-279, A1Kinematics fk / jac restated from the leg model), one lane per (robot, leg) -----------
@@ -1142,48 +1207,31 @@ __global__ __launch_bounds__(256) void a1mpc_leg_kernel(const LegArgs a) {
     ws.flush3(va, pw, vw, a.vabs, a.pworld, a.vworld);
 }
 
+// (the five outputs after j_foot_blocks are optional: null = not wanted)
+static void launch_leg(int32_t n, const double* rho_fix, const double* rho_opt, const double* joint_pos, const double* joint_vel, const double* R_world, const double* root_pos,
+                       const double* root_lin_vel, double* foot_pos_rel_out, double* j_foot_blocks_out, double* foot_vel_rel_out, double* foot_pos_abs_out,
+                       double* foot_vel_abs_out, double* foot_pos_world_out, double* foot_vel_world_out, hipStream_t s) {
+    LegArgs a;
+    a.n = n;
+    std::memcpy(a.rho_fix, rho_fix, sizeof a.rho_fix); std::memcpy(a.rho_opt, rho_opt, sizeof a.rho_opt);
+    a.q = joint_pos; a.qd = joint_vel; a.R = R_world; a.pos = root_pos; a.vel = root_lin_vel; a.rel = foot_pos_rel_out; a.Jb = j_foot_blocks_out;
+    a.vrel = foot_vel_rel_out; a.pabs = foot_pos_abs_out; a.vabs = foot_vel_abs_out; a.pworld = foot_pos_world_out; a.vworld = foot_vel_world_out;
+    hipLaunchKernelGGL(a1mpc_leg_kernel, leg_lane_grid(n), dim3(256), 0, s, a);
+}
+
 a1mpc_status a1mpc_leg_state_batch(a1mpc_handle h, int32_t n, const double* joint_pos, const double* joint_vel, const double* R_world,
                                    const double* root_pos, const double* root_lin_vel, const double* rho_fix, const double* rho_opt,
                                    double* foot_pos_rel_out, double* j_foot_blocks_out, double* foot_vel_rel_out, double* foot_pos_abs_out,
                                    double* foot_vel_abs_out, double* foot_pos_world_out, double* foot_vel_world_out) {
-    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || !joint_pos || !joint_vel || !R_world || !root_pos || !root_lin_vel || !rho_fix || !rho_opt || !foot_pos_rel_out || !j_foot_blocks_out)
-        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    // staging: aux_in [q 12 | qd 12 | R 9 | pos 3 | vel 3 | rel 12] = 51 of 64, aux_out [Jb 36 | vrel 12 | pabs 12 | vabs 12 | pworld 12 | vworld 12] = 96
-    double *d_q = h->d_aux_in, *d_qd = d_q + 12 * N, *d_R = d_qd + 12 * N, *d_pos = d_R + 9 * N, *d_vel = d_pos + 3 * N, *d_rel = d_vel + 3 * N;
-    double *d_Jb = h->d_aux_out, *d_vrel = d_Jb + 36 * N, *d_pabs = d_vrel + 12 * N, *d_vabs = d_pabs + 12 * N, *d_pw = d_vabs + 12 * N, *d_vw = d_pw + 12 * N;
-    A1_HIP(hipMemcpyAsync(d_q, joint_pos, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_qd, joint_vel, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_pos, root_pos, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_vel, root_lin_vel, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    LegArgs a;
-    a.n = n;
-    std::memcpy(a.rho_fix, rho_fix, sizeof a.rho_fix); std::memcpy(a.rho_opt, rho_opt, sizeof a.rho_opt);
-    a.q = d_q; a.qd = d_qd; a.R = d_R; a.pos = d_pos; a.vel = d_vel; a.rel = d_rel; a.Jb = d_Jb;
-    a.vrel = foot_vel_rel_out ? d_vrel : nullptr; a.pabs = foot_pos_abs_out ? d_pabs : nullptr; a.vabs = foot_vel_abs_out ? d_vabs : nullptr;
-    a.pworld = foot_pos_world_out ? d_pw : nullptr; a.vworld = foot_vel_world_out ? d_vw : nullptr;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_leg_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(foot_pos_rel_out, d_rel, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(j_foot_blocks_out, d_Jb, N * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (foot_vel_rel_out) A1_HIP(hipMemcpyAsync(foot_vel_rel_out, d_vrel, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (foot_pos_abs_out) A1_HIP(hipMemcpyAsync(foot_pos_abs_out, d_pabs, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (foot_vel_abs_out) A1_HIP(hipMemcpyAsync(foot_vel_abs_out, d_vabs, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (foot_pos_world_out) A1_HIP(hipMemcpyAsync(foot_pos_world_out, d_pw, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (foot_vel_world_out) A1_HIP(hipMemcpyAsync(foot_vel_world_out, d_vw, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
-    return A1MPC_OK;
+    A1_STAGE_BEGIN(joint_pos && joint_vel && R_world && root_pos && root_lin_vel && rho_fix && rho_opt && foot_pos_rel_out && j_foot_blocks_out,
+                   "null input/output pointer", nullptr);
+    Staging sg(h, n, s);
+    const double *d_q = sg.in(joint_pos, 12), *d_qd = sg.in(joint_vel, 12), *d_R = sg.in(R_world, 9), *d_pos = sg.in(root_pos, 3), *d_vel = sg.in(root_lin_vel, 3);
+    double *d_rel = sg.out(foot_pos_rel_out, 12), *d_Jb = sg.out(j_foot_blocks_out, 36), *d_vrel = sg.out(foot_vel_rel_out, 12), *d_pabs = sg.out(foot_pos_abs_out, 12);
+    double *d_vabs = sg.out(foot_vel_abs_out, 12), *d_pw = sg.out(foot_pos_world_out, 12), *d_vw = sg.out(foot_vel_world_out, 12);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_leg(n, rho_fix, rho_opt, d_q, d_qd, d_R, d_pos, d_vel, d_rel, d_Jb, d_vrel, d_pabs, d_vabs, d_pw, d_vw, s));
+    return sg.finish();
 }
 
 // ---- N4c: A1BasicEKF (S/A1BasicEKF.cpp), 32 lanes per robot, two robots per wavefront -----------------------------------------------
@@ -1458,54 +1506,46 @@ a1mpc_status a1mpc_reset_ekf_state(a1mpc_handle h) {
     h->ekf_ready_n = 0;
     return A1MPC_OK;
 }
-a1mpc_status a1mpc_ekf_update_batch(a1mpc_handle h, int32_t n, double dt, int32_t assume_flat_ground, const uint8_t* movement_mode,
-                                    const double* foot_force, const double* R_world, const double* imu_acc, const double* imu_ang_vel,
-                                    const double* foot_pos_rel, const double* foot_vel_rel, double* root_pos_out, double* root_lin_vel_out,
-                                    uint8_t* estimated_contacts_out) {
-    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || !movement_mode || !foot_force || !R_world || !imu_acc || !imu_ang_vel || !foot_pos_rel || !foot_vel_rel || !root_pos_out ||
-        !root_lin_vel_out || !estimated_contacts_out || !(dt > 0))
-        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer or dt <= 0");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    if (!h->d_ekf_state) {
-        A1_HIP(hipMalloc(&h->d_ekf_state, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double)));
-        A1_HIP(hipMemsetAsync(h->d_ekf_state, 0, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double), s));
-    }
-    // staging: aux_in [ff 4 | R 9 | acc 3 | w 3 | fk 12 | fv 12] = 43, aux_out [pos 3 | vel 3]
-    double *d_ff = h->d_aux_in, *d_R = d_ff + 4 * N, *d_acc = d_R + 9 * N, *d_w = d_acc + 3 * N, *d_fk = d_w + 3 * N, *d_fv = d_fk + 12 * N;
-    double *d_pos = h->d_aux_out, *d_vel = d_pos + 3 * N;
-    uint8_t *d_mm = h->d_aux_u8, *d_ec = h->d_aux_u8 + 8 * N;
-    A1_HIP(hipMemcpyAsync(d_ff, foot_force, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_acc, imu_acc, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_w, imu_ang_vel, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_fk, foot_pos_rel, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_fv, foot_vel_rel, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_mm, movement_mode, N, hipMemcpyHostToDevice, s));
+// the handle's filter state, allocated on first use (zero = not initialised: a1mpc_ekf_init_kernel)
+static a1mpc_status ensure_ekf_state(a1mpc_handle h, hipStream_t s) {
+    if (h->d_ekf_state) return A1MPC_OK;
+    A1_HIP(hipMalloc(&h->d_ekf_state, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double)));
+    A1_HIP(hipMemsetAsync(h->d_ekf_state, 0, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double), s));
+    return A1MPC_OK;
+}
+// the init kernel for robots that have not been through it, then the update kernel (whose launch status is the caller's to read)
+static a1mpc_status launch_ekf(a1mpc_handle h, int32_t n, double dt, int32_t assume_flat_ground, const uint8_t* movement_mode, const double* foot_force, const double* R_world,
+                               const double* imu_acc, const double* imu_ang_vel, const double* foot_pos_rel, const double* foot_vel_rel, double* root_pos_out,
+                               double* root_lin_vel_out, uint8_t* estimated_contacts_out, hipStream_t s) {
     EkfArgs a;
-    a.n = n; a.dt = dt; a.flat = assume_flat_ground; a.state = h->d_ekf_state; a.mode = d_mm; a.ff = d_ff; a.R = d_R; a.acc = d_acc; a.w = d_w;
-    a.fk = d_fk; a.fv = d_fv; a.pos_out = d_pos; a.vel_out = d_vel; a.ec_out = d_ec;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
+    a.n = n; a.dt = dt; a.flat = assume_flat_ground; a.state = h->d_ekf_state; a.mode = movement_mode; a.ff = foot_force; a.R = R_world; a.acc = imu_acc;
+    a.w = imu_ang_vel; a.fk = foot_pos_rel; a.fv = foot_vel_rel; a.pos_out = root_pos_out; a.vel_out = root_lin_vel_out; a.ec_out = estimated_contacts_out;
     if (n > h->ekf_ready_n) {   // (robots 0 .. ekf_ready_n - 1 have been through init_state: nothing for the init kernel to do -- one launch less per tick)
-        hipLaunchKernelGGL(a1mpc_ekf_init_kernel, dim3(static_cast<unsigned>((N + 255) / 256)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(a1mpc_ekf_init_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 255) / 256)), dim3(256), 0, s, a);
         if (hipError_t ei = hipGetLastError(); ei != hipSuccess) { h->ekf_ready_n = 0; return fail(A1MPC_ERR_HIP, std::string("a1mpc_ekf_init_kernel: ") + hipGetErrorString(ei)); }
         h->ekf_ready_n = n;   // (only once the launch has been accepted -- ADVICE r5: a failed init launch must not leave the robots marked as initialised)
     }
     launch_ekf_update(a, s);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(root_pos_out, d_pos, N * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(root_lin_vel_out, d_vel, N * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(estimated_contacts_out, d_ec, N * 4, hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
     return A1MPC_OK;
+}
+#define A1_LAUNCH_EKF(...) if (a1mpc_status se_ = launch_ekf(__VA_ARGS__); se_ != A1MPC_OK) return se_
+
+a1mpc_status a1mpc_ekf_update_batch(a1mpc_handle h, int32_t n, double dt, int32_t assume_flat_ground, const uint8_t* movement_mode,
+                                    const double* foot_force, const double* R_world, const double* imu_acc, const double* imu_ang_vel,
+                                    const double* foot_pos_rel, const double* foot_vel_rel, double* root_pos_out, double* root_lin_vel_out,
+                                    uint8_t* estimated_contacts_out) {
+    A1_STAGE_BEGIN(movement_mode && foot_force && R_world && imu_acc && imu_ang_vel && foot_pos_rel && foot_vel_rel && root_pos_out && root_lin_vel_out &&
+                   estimated_contacts_out && dt > 0, "null input/output pointer or dt <= 0", nullptr);
+    Staging sg(h, n, s);
+    if (a1mpc_status st = ensure_ekf_state(h, s); st != A1MPC_OK) return st;
+    const double *d_ff = sg.in(foot_force, 4), *d_R = sg.in(R_world, 9), *d_acc = sg.in(imu_acc, 3), *d_w = sg.in(imu_ang_vel, 3), *d_fk = sg.in(foot_pos_rel, 12);
+    const double* d_fv = sg.in(foot_vel_rel, 12);
+    const uint8_t* d_mm = sg.in(movement_mode, 1);
+    double *d_pos = sg.out(root_pos_out, 3), *d_vel = sg.out(root_lin_vel_out, 3);
+    uint8_t* d_ec = sg.out(estimated_contacts_out, 4);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(A1_LAUNCH_EKF(h, n, dt, assume_flat_ground, d_mm, d_ff, d_R, d_acc, d_w, d_fk, d_fv, d_pos, d_vel, d_ec, s));
+    return sg.finish();
 }
 
 // ---- N3: compute_joint_torques (S/A1RobotControl.cpp:289-319), one lane per (robot, leg); no FMA contraction ---------------------
@@ -1536,40 +1576,25 @@ __global__ __launch_bounds__(256) void a1mpc_torque_kernel(const TorqueArgs a) {
     if (!isnan(v2)) out[2] = v2;
 }
 
+static void launch_torque(int32_t n, const uint8_t* active, const uint8_t* contacts, const double* j_foot_blocks, const double* grf, const double* f_kin, const double* km_foot,
+                          const double* torques_gravity, double* joint_torques, hipStream_t s) {
+    TorqueArgs a;
+    a.n = n; a.active = active; a.contacts = contacts; a.Jb = j_foot_blocks; a.grf = grf; a.fkin = f_kin; a.tg = torques_gravity; a.tau = joint_torques;
+    a.km[0] = km_foot[0]; a.km[1] = km_foot[1]; a.km[2] = km_foot[2];
+    hipLaunchKernelGGL(a1mpc_torque_kernel, leg_lane_grid(n), dim3(256), 0, s, a);
+}
+
 a1mpc_status a1mpc_joint_torques_batch(a1mpc_handle h, int32_t n, const uint8_t* active, const uint8_t* contacts, const double* j_foot_blocks,
                                        const double* grf, const double* f_kin, const double* km_foot, const double* torques_gravity,
                                        double* joint_torques) {
-    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || !active || !contacts || !j_foot_blocks || !grf || !f_kin || !km_foot || !torques_gravity || !joint_torques)
-        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    // staging: in [J 36 | grf 12 | f_kin 12], out [tg 12 | tau 12]
-    double *d_J = h->d_aux_in, *d_grf = d_J + 36 * N, *d_fk = d_grf + 12 * N, *d_tg = h->d_aux_out, *d_tau = d_tg + 12 * N;
-    uint8_t *d_c = h->d_aux_u8, *d_act = h->d_aux_u8 + 8 * N;
-    A1_HIP(hipMemcpyAsync(d_J, j_foot_blocks, N * 36 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_grf, grf, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_fk, f_kin, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_tg, torques_gravity, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_tau, joint_torques, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_c, contacts, N * 4, hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_act, active, N, hipMemcpyHostToDevice, s));
-    TorqueArgs a;
-    a.n = n; a.active = d_act; a.contacts = d_c; a.Jb = d_J; a.grf = d_grf; a.fkin = d_fk; a.tg = d_tg; a.tau = d_tau;
-    a.km[0] = km_foot[0]; a.km[1] = km_foot[1]; a.km[2] = km_foot[2];
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_torque_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(joint_torques, d_tau, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
-    return A1MPC_OK;
+    A1_STAGE_BEGIN(active && contacts && j_foot_blocks && grf && f_kin && km_foot && torques_gravity && joint_torques, "null input/output pointer", nullptr);
+    Staging sg(h, n, s);
+    const double *d_J = sg.in(j_foot_blocks, 36), *d_grf = sg.in(grf, 12), *d_fk = sg.in(f_kin, 12), *d_tg = sg.in(torques_gravity, 12);
+    double* d_tau = sg.inout(joint_torques, 12);   // (in as well: a NaN component leaves the caller's value, :314-317)
+    const uint8_t *d_c = sg.in(contacts, 4), *d_act = sg.in(active, 1);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_torque(n, d_act, d_c, d_J, d_grf, d_fk, km_foot, d_tg, d_tau, s));
+    return sg.finish();
 }
 
 void a1mpc_default_gait_config(a1mpc_gait_config* g) {
@@ -1584,163 +1609,98 @@ void a1mpc_default_gait_config(a1mpc_gait_config* g) {
     std::memcpy(g->gait_counter_reset, rs, sizeof rs);
 }
 
+// (rel / abs / world are optional outputs: null = not wanted)
+static PlanArgs make_plan_args(const a1mpc_gait_config& gait, int32_t n, const uint8_t* movement_mode, double* gait_counter, const double* gait_counter_speed,
+                               const double* root_lin_vel, const double* R_z, const double* R_world, const double* root_pos, const double* root_lin_vel_d,
+                               uint8_t* plan_contacts_out, double* rel_out, double* abs_out, double* world_out) {
+    PlanArgs a;
+    a.g = gait; a.n = n; a.movement_mode = movement_mode; a.gait_counter = gait_counter; a.gait_counter_speed = gait_counter_speed; a.root_lin_vel = root_lin_vel;
+    a.Rz = R_z; a.Rw = R_world; a.root_pos = root_pos; a.root_lin_vel_d = root_lin_vel_d; a.plan_contacts = plan_contacts_out; a.rel = rel_out; a.abs_ = abs_out;
+    a.world = world_out;
+    return a;
+}
+static void launch_plan(const PlanArgs& a, hipStream_t s) { hipLaunchKernelGGL(a1mpc_plan_kernel, leg_lane_grid(a.n), dim3(256), 0, s, a); }
+
 a1mpc_status a1mpc_update_plan_batch(a1mpc_handle h, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
                                      double* gait_counter, const double* gait_counter_speed, const double* root_lin_vel,
                                      const double* R_z, const double* R_world, const double* root_pos, const double* root_lin_vel_d,
                                      uint8_t* plan_contacts_out, double* rel_out, double* abs_out, double* world_out) {
-    if (!h || !gait) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle/config");
-    if (n < 0 || !movement_mode || !gait_counter || !gait_counter_speed || !root_lin_vel || !R_z || !R_world || !root_pos || !root_lin_vel_d ||
-        !plan_contacts_out)
-        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    // staging: in [gc 4 | spd 4 | v 3 | vd 3 | pos 3 | Rz 9 | Rw 9], out [rel 12 | abs 12 | world 12]
-    double* din = h->d_aux_in;
-    double *d_gc = din, *d_spd = d_gc + 4 * N, *d_v = d_spd + 4 * N, *d_vd = d_v + 3 * N, *d_pos = d_vd + 3 * N, *d_Rz = d_pos + 3 * N, *d_Rw = d_Rz + 9 * N;
-    double *d_rel = h->d_aux_out, *d_abs = d_rel + 12 * N, *d_world = d_abs + 12 * N;
-    uint8_t *d_mm = h->d_aux_u8, *d_pc = h->d_aux_u8 + 8 * N;
-    A1_HIP(hipMemcpyAsync(d_gc, gait_counter, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_spd, gait_counter_speed, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_v, root_lin_vel, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_vd, root_lin_vel_d, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_pos, root_pos, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_Rz, R_z, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_Rw, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_mm, movement_mode, N, hipMemcpyHostToDevice, s));
-    PlanArgs a;
-    a.g = *gait; a.n = n; a.movement_mode = d_mm; a.gait_counter = d_gc; a.gait_counter_speed = d_spd; a.root_lin_vel = d_v; a.Rz = d_Rz; a.Rw = d_Rw;
-    a.root_pos = d_pos; a.root_lin_vel_d = d_vd; a.plan_contacts = d_pc; a.rel = d_rel; a.abs_ = d_abs; a.world = d_world;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_plan_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(gait_counter, d_gc, N * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(plan_contacts_out, d_pc, N * 4, hipMemcpyDeviceToHost, s));
-    if (rel_out) A1_HIP(hipMemcpyAsync(rel_out, d_rel, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (abs_out) A1_HIP(hipMemcpyAsync(abs_out, d_abs, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (world_out) A1_HIP(hipMemcpyAsync(world_out, d_world, N * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
-    return A1MPC_OK;
+    A1_STAGE_BEGIN(gait && movement_mode && gait_counter && gait_counter_speed && root_lin_vel && R_z && R_world && root_pos && root_lin_vel_d && plan_contacts_out,
+                   "null config or input/output pointer", nullptr);
+    Staging sg(h, n, s);
+    double* d_gc = sg.inout(gait_counter, 4);
+    const double *d_spd = sg.in(gait_counter_speed, 4), *d_v = sg.in(root_lin_vel, 3), *d_vd = sg.in(root_lin_vel_d, 3), *d_pos = sg.in(root_pos, 3);
+    const double *d_Rz = sg.in(R_z, 9), *d_Rw = sg.in(R_world, 9);
+    const uint8_t* d_mm = sg.in(movement_mode, 1);
+    uint8_t* d_pc = sg.out(plan_contacts_out, 4);
+    double *d_rel = sg.out(rel_out, 12), *d_abs = sg.out(abs_out, 12), *d_world = sg.out(world_out, 12);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_plan(make_plan_args(*gait, n, d_mm, d_gc, d_spd, d_v, d_Rz, d_Rw, d_pos, d_vd, d_pc, d_rel, d_abs, d_world), s));
+    return sg.finish();
 }
 
 // ---- device-pointer variants of the caller-side entry points: every array is device-resident, the call is asynchronous on `hip_stream`
 // (NULL = the handle's stream), so a whole control tick -- leg state, EKF, plan, swing legs, contacts / terrain, MPC, joint torques --
 // chains on the GPU without a PCIe hop.  Same kernels as the host-pointer entries.
-#define A1_DEV_PROLOGUE(cond)                                                                               \
-    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");                                          \
-    if (n < 0 || !(cond)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");              \
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");      \
-    if (n == 0) return A1MPC_OK;                                                                             \
-    A1_HIP(hipSetDevice(h->device));                                                                         \
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;                           \
-    A1_ORDER(h, s);                                                                                          \
-    const size_t N = n;                                                                                      \
-    (void)N
-#define A1_DEV_EPILOGUE()              \
-    A1_HIP(hipGetLastError());         \
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s)); \
-    h->timed = h->timing; A1_MARK(h, s); \
-    return A1MPC_OK
-
 a1mpc_status a1mpc_update_plan_batch_device(a1mpc_handle h, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
                                             double* gait_counter, const double* gait_counter_speed, const double* root_lin_vel, const double* R_z,
                                             const double* R_world, const double* root_pos, const double* root_lin_vel_d, uint8_t* plan_contacts_out,
                                             double* rel_out, double* abs_out, double* world_out, void* hip_stream) {
-    A1_DEV_PROLOGUE(gait && movement_mode && gait_counter && gait_counter_speed && root_lin_vel && R_z && R_world && root_pos && root_lin_vel_d && plan_contacts_out);
-    PlanArgs a;
-    a.g = *gait; a.n = n; a.movement_mode = movement_mode; a.gait_counter = gait_counter; a.gait_counter_speed = gait_counter_speed; a.root_lin_vel = root_lin_vel;
-    a.Rz = R_z; a.Rw = R_world; a.root_pos = root_pos; a.root_lin_vel_d = root_lin_vel_d; a.plan_contacts = plan_contacts_out; a.rel = rel_out; a.abs_ = abs_out;
-    a.world = world_out;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_plan_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_DEV_EPILOGUE();
+    A1_STAGE_BEGIN(gait && movement_mode && gait_counter && gait_counter_speed && root_lin_vel && R_z && R_world && root_pos && root_lin_vel_d && plan_contacts_out,
+                   "null config or input/output pointer", hip_stream);
+    A1_STAGE_LAUNCH(launch_plan(make_plan_args(*gait, n, movement_mode, gait_counter, gait_counter_speed, root_lin_vel, R_z, R_world, root_pos, root_lin_vel_d, plan_contacts_out,
+                                               rel_out, abs_out, world_out), s));
+    return A1MPC_OK;
 }
 a1mpc_status a1mpc_swing_legs_batch_device(a1mpc_handle h, int32_t n, double counter_per_swing, double dt, const double* R_z, const double* foot_pos_abs,
                                            const double* gait_counter, const double* foot_pos_target_rel, const double* kp_foot_host, const double* kd_foot_host,
                                            double* foot_pos_start, double* foot_pos_rel_last_time, double* foot_pos_target_last_time, double* foot_pos_cur_out,
                                            double* foot_forces_kin_out, void* hip_stream) {
-    A1_DEV_PROLOGUE(R_z && foot_pos_abs && gait_counter && foot_pos_target_rel && kp_foot_host && kd_foot_host && foot_pos_start && foot_pos_rel_last_time &&
-                    foot_pos_target_last_time && foot_pos_cur_out && foot_forces_kin_out && dt > 0);
-    SwingArgs a;
-    a.n = n; a.counter_per_swing = counter_per_swing; a.dt = dt;
-    for (int k = 0; k < 3; ++k) { a.kp[k] = kp_foot_host[k]; a.kd[k] = kd_foot_host[k]; }
-    a.Rz = R_z; a.foot_pos_abs = foot_pos_abs; a.gait_counter = gait_counter; a.target_rel = foot_pos_target_rel; a.start = foot_pos_start;
-    a.rel_last = foot_pos_rel_last_time; a.target_last = foot_pos_target_last_time; a.cur_out = foot_pos_cur_out; a.kin_out = foot_forces_kin_out;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_swing_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_DEV_EPILOGUE();
+    A1_STAGE_BEGIN(R_z && foot_pos_abs && gait_counter && foot_pos_target_rel && kp_foot_host && kd_foot_host && foot_pos_start && foot_pos_rel_last_time &&
+                   foot_pos_target_last_time && foot_pos_cur_out && foot_forces_kin_out && dt > 0, "null input/output pointer or dt <= 0", hip_stream);
+    A1_STAGE_LAUNCH(launch_swing(make_swing_args(n, counter_per_swing, dt, kp_foot_host, kd_foot_host, R_z, foot_pos_abs, gait_counter, foot_pos_target_rel, foot_pos_start,
+                                                 foot_pos_rel_last_time, foot_pos_target_last_time, foot_pos_cur_out, foot_forces_kin_out), s));
+    return A1MPC_OK;
 }
 a1mpc_status a1mpc_contact_terrain_batch_device(a1mpc_handle h, const a1mpc_contact_config* cfg, int32_t n, const double* gait_counter,
                                                 const uint8_t* plan_contacts, const double* foot_force, const double* foot_pos_abs, const double* root_pos_z,
                                                 double* root_euler_d_pitch, uint8_t* contacts_out, double* foot_pos_recent_contact_out, double* terrain_angle_out,
                                                 void* hip_stream) {
-    A1_DEV_PROLOGUE(cfg && gait_counter && plan_contacts && foot_force && foot_pos_abs && root_pos_z && root_euler_d_pitch && contacts_out &&
-                    foot_pos_recent_contact_out && terrain_angle_out);
+    A1_STAGE_BEGIN(cfg && gait_counter && plan_contacts && foot_force && foot_pos_abs && root_pos_z && root_euler_d_pitch && contacts_out &&
+                   foot_pos_recent_contact_out && terrain_angle_out, "null config or input/output pointer", hip_stream);
     if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
-    ContactArgs a;
-    a.recent_in = nullptr; a.z_stride = 1; a.pitch_stride = 1; a.pk_tick = nullptr;
-    a.n = n; a.counter_per_swing = cfg->counter_per_swing; a.foot_force_low = cfg->foot_force_low; a.use_terrain_adapt = cfg->use_terrain_adapt;
-    contact_state_pointers(h, a); a.gait_counter = gait_counter; a.foot_force = foot_force; a.foot_pos_abs = foot_pos_abs; a.root_pos_z = root_pos_z;
-    a.plan_contacts = plan_contacts; a.pitch_d = root_euler_d_pitch; a.contacts = contacts_out; a.recent_out = foot_pos_recent_contact_out; a.terrain_out = terrain_angle_out;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    launch_contact_terrain(a, s);
-    A1_DEV_EPILOGUE();
+    A1_STAGE_LAUNCH(launch_contact_terrain(make_contact_args(h, *cfg, n, gait_counter, plan_contacts, foot_force, foot_pos_abs, root_pos_z, root_euler_d_pitch, contacts_out,
+                                                             foot_pos_recent_contact_out, terrain_angle_out), s));
+    return A1MPC_OK;
 }
 a1mpc_status a1mpc_leg_state_batch_device(a1mpc_handle h, int32_t n, const double* joint_pos, const double* joint_vel, const double* R_world,
                                           const double* root_pos, const double* root_lin_vel, const double* rho_fix_host, const double* rho_opt_host,
                                           double* foot_pos_rel_out, double* j_foot_blocks_out, double* foot_vel_rel_out, double* foot_pos_abs_out,
                                           double* foot_vel_abs_out, double* foot_pos_world_out, double* foot_vel_world_out, void* hip_stream) {
-    A1_DEV_PROLOGUE(joint_pos && joint_vel && R_world && root_pos && root_lin_vel && rho_fix_host && rho_opt_host && foot_pos_rel_out && j_foot_blocks_out);
-    LegArgs a;
-    a.n = n;
-    std::memcpy(a.rho_fix, rho_fix_host, sizeof a.rho_fix); std::memcpy(a.rho_opt, rho_opt_host, sizeof a.rho_opt);
-    a.q = joint_pos; a.qd = joint_vel; a.R = R_world; a.pos = root_pos; a.vel = root_lin_vel; a.rel = foot_pos_rel_out; a.Jb = j_foot_blocks_out;
-    a.vrel = foot_vel_rel_out; a.pabs = foot_pos_abs_out; a.vabs = foot_vel_abs_out; a.pworld = foot_pos_world_out; a.vworld = foot_vel_world_out;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_leg_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_DEV_EPILOGUE();
+    A1_STAGE_BEGIN(joint_pos && joint_vel && R_world && root_pos && root_lin_vel && rho_fix_host && rho_opt_host && foot_pos_rel_out && j_foot_blocks_out,
+                   "null input/output pointer", hip_stream);
+    A1_STAGE_LAUNCH(launch_leg(n, rho_fix_host, rho_opt_host, joint_pos, joint_vel, R_world, root_pos, root_lin_vel, foot_pos_rel_out, j_foot_blocks_out, foot_vel_rel_out,
+                               foot_pos_abs_out, foot_vel_abs_out, foot_pos_world_out, foot_vel_world_out, s));
+    return A1MPC_OK;
 }
 a1mpc_status a1mpc_ekf_update_batch_device(a1mpc_handle h, int32_t n, double dt, int32_t assume_flat_ground, const uint8_t* movement_mode,
                                            const double* foot_force, const double* R_world, const double* imu_acc, const double* imu_ang_vel,
                                            const double* foot_pos_rel, const double* foot_vel_rel, double* root_pos_out, double* root_lin_vel_out,
                                            uint8_t* estimated_contacts_out, void* hip_stream) {
-    A1_DEV_PROLOGUE(movement_mode && foot_force && R_world && imu_acc && imu_ang_vel && foot_pos_rel && foot_vel_rel && root_pos_out && root_lin_vel_out &&
-                    estimated_contacts_out && dt > 0);
-    if (!h->d_ekf_state) {
-        A1_HIP(hipMalloc(&h->d_ekf_state, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double)));
-        A1_HIP(hipMemsetAsync(h->d_ekf_state, 0, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double), s));
-    }
-    EkfArgs a;
-    a.n = n; a.dt = dt; a.flat = assume_flat_ground; a.state = h->d_ekf_state; a.mode = movement_mode; a.ff = foot_force; a.R = R_world; a.acc = imu_acc;
-    a.w = imu_ang_vel; a.fk = foot_pos_rel; a.fv = foot_vel_rel; a.pos_out = root_pos_out; a.vel_out = root_lin_vel_out; a.ec_out = estimated_contacts_out;
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    if (n > h->ekf_ready_n) {   // (robots 0 .. ekf_ready_n - 1 have been through init_state: nothing for the init kernel to do -- one launch less per tick)
-        hipLaunchKernelGGL(a1mpc_ekf_init_kernel, dim3(static_cast<unsigned>((N + 255) / 256)), dim3(256), 0, s, a);
-        if (hipError_t ei = hipGetLastError(); ei != hipSuccess) { h->ekf_ready_n = 0; return fail(A1MPC_ERR_HIP, std::string("a1mpc_ekf_init_kernel: ") + hipGetErrorString(ei)); }
-        h->ekf_ready_n = n;   // (only once the launch has been accepted -- ADVICE r5: a failed init launch must not leave the robots marked as initialised)
-    }
-    launch_ekf_update(a, s);
-    A1_DEV_EPILOGUE();
+    A1_STAGE_BEGIN(movement_mode && foot_force && R_world && imu_acc && imu_ang_vel && foot_pos_rel && foot_vel_rel && root_pos_out && root_lin_vel_out &&
+                   estimated_contacts_out && dt > 0, "null input/output pointer or dt <= 0", hip_stream);
+    if (a1mpc_status st = ensure_ekf_state(h, s); st != A1MPC_OK) return st;
+    A1_STAGE_LAUNCH(A1_LAUNCH_EKF(h, n, dt, assume_flat_ground, movement_mode, foot_force, R_world, imu_acc, imu_ang_vel, foot_pos_rel, foot_vel_rel, root_pos_out,
+                                  root_lin_vel_out, estimated_contacts_out, s));
+    return A1MPC_OK;
 }
 a1mpc_status a1mpc_joint_torques_batch_device(a1mpc_handle h, int32_t n, const uint8_t* active, const uint8_t* contacts, const double* j_foot_blocks,
                                               const double* grf, const double* f_kin, const double* km_foot_host, const double* torques_gravity,
                                               double* joint_torques, void* hip_stream) {
-    A1_DEV_PROLOGUE(active && contacts && j_foot_blocks && grf && f_kin && km_foot_host && torques_gravity && joint_torques);
-    TorqueArgs a;
-    a.n = n; a.active = active; a.contacts = contacts; a.Jb = j_foot_blocks; a.grf = grf; a.fkin = f_kin; a.tg = torques_gravity; a.tau = joint_torques;
-    a.km[0] = km_foot_host[0]; a.km[1] = km_foot_host[1]; a.km[2] = km_foot_host[2];
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    hipLaunchKernelGGL(a1mpc_torque_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    A1_DEV_EPILOGUE();
+    A1_STAGE_BEGIN(active && contacts && j_foot_blocks && grf && f_kin && km_foot_host && torques_gravity && joint_torques, "null input/output pointer", hip_stream);
+    A1_STAGE_LAUNCH(launch_torque(n, active, contacts, j_foot_blocks, grf, f_kin, km_foot_host, torques_gravity, joint_torques, s));
+    return A1MPC_OK;
 }
-#undef A1_DEV_PROLOGUE
-#undef A1_DEV_EPILOGUE
 
 const char* a1mpc_status_string(a1mpc_status s) {
     switch (s) {
@@ -2280,7 +2240,7 @@ static void launch_preview(a1mpc_handle h, const a1mpc_preview_config& pv, doubl
     a.movement_mode = movement_mode; a.contacts = contacts; a.gait_counter = gait_counter; a.gait_counter_speed = gait_counter_speed;
     a.foot_pos_abs = foot_pos_abs; a.Rw = R_world; a.root_lin_vel_d = root_lin_vel_d;
     a.sched = reinterpret_cast<uint32_t*>(sched_out); a.foot_steps = foot_steps_out;
-    hipLaunchKernelGGL(a1mpc_horizon_preview_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) * 4 + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(a1mpc_horizon_preview_kernel, leg_lane_grid(n), dim3(256), 0, s, a);
 }
 // pointer rules shared by the two preview entries: each output needs its inputs
 static const char* invalid_preview_io(const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, const uint8_t* movement_mode, const double* gait_counter,
@@ -2303,17 +2263,9 @@ a1mpc_status a1mpc_horizon_preview_batch_device(a1mpc_handle h, const a1mpc_prev
     if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
     if (const char* bad = invalid_preview_io(pv, gait, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, sched_out, foot_steps_out, true))
         return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
-    A1_ORDER(h, s);
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d,
-                   sched_out, foot_steps_out, s);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world,
+                                   root_lin_vel_d, sched_out, foot_steps_out, s));
     return A1MPC_OK;
 }
 // the handle's per-step staging (a1mpc_solve_batch_strided's too): n x 12H feet, n x 4H contact bytes
@@ -2331,35 +2283,24 @@ a1mpc_status a1mpc_horizon_preview_batch(a1mpc_handle h, const a1mpc_preview_con
     if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
     if (const char* bad = invalid_preview_io(pv, gait, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, sched_out, foot_steps_out,
                                              false)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);   // (a host array for the schedule may sit at any address: it is staged)
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
     if (a1mpc_status st = ensure_step_staging(h); st != A1MPC_OK) return st;
-    const size_t N = n, H = h->cfg.horizon;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    // staging: in [gc 4 | spd 4 | foot 12 | R 9 | vd 3] + bytes [mode 1 .. | contacts 4 from 8 N], out: the handle's per-step buffers
-    double *d_gc = h->d_aux_in, *d_spd = d_gc + 4 * N, *d_fp = d_spd + 4 * N, *d_R = d_fp + 12 * N, *d_vd = d_R + 9 * N;
-    uint8_t *d_mm = h->d_aux_u8, *d_ct = h->d_aux_u8 + 8 * N;
-    if (gait_counter) A1_HIP(hipMemcpyAsync(d_gc, gait_counter, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (gait_counter_speed) A1_HIP(hipMemcpyAsync(d_spd, gait_counter_speed, N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (foot_pos_abs) A1_HIP(hipMemcpyAsync(d_fp, foot_pos_abs, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (R_world) A1_HIP(hipMemcpyAsync(d_R, R_world, N * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (root_lin_vel_d) A1_HIP(hipMemcpyAsync(d_vd, root_lin_vel_d, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (movement_mode) A1_HIP(hipMemcpyAsync(d_mm, movement_mode, N, hipMemcpyHostToDevice, s));
-    if (contacts) A1_HIP(hipMemcpyAsync(d_ct, contacts, N * 4, hipMemcpyHostToDevice, s));
-    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
-    launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, d_mm, d_gc, d_spd, d_ct, d_fp, d_R, d_vd, sched_out ? h->d_contact_steps : nullptr,
-                   foot_steps_out ? h->d_foot_steps : nullptr, s);
-    A1_HIP(hipGetLastError());
-    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
-    h->timed = h->timing; A1_MARK(h, s);
-    if (sched_out) A1_HIP(hipMemcpyAsync(sched_out, h->d_contact_steps, N * 4 * H, hipMemcpyDeviceToHost, s));
-    if (foot_steps_out) A1_HIP(hipMemcpyAsync(foot_steps_out, h->d_foot_steps, N * 12 * H * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
-    return A1MPC_OK;
+    // (an input that the configured preview does not read may be null: its slice is handed to the kernel unfilled.)  Out: the handle's per-step buffers
+    const double *d_gc = sg.in(gait_counter, 4), *d_spd = sg.in(gait_counter_speed, 4), *d_fp = sg.in(foot_pos_abs, 12), *d_R = sg.in(R_world, 9), *d_vd = sg.in(root_lin_vel_d, 3);
+    const uint8_t *d_mm = sg.in(movement_mode, 1), *d_ct = sg.in(contacts, 4);
+    const size_t H = h->cfg.horizon;
+    sg.back(sched_out, h->d_contact_steps, 4 * H);
+    sg.back(foot_steps_out, h->d_foot_steps, 12 * H);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, d_mm, d_gc, d_spd, d_ct, d_fp, d_R, d_vd, sched_out ? h->d_contact_steps : nullptr,
+                                   foot_steps_out ? h->d_foot_steps : nullptr, s));
+    return sg.finish();
 }
+#undef A1_STAGE_BEGIN
+#undef A1_STAGE_DEVICE
+#undef A1_STAGE_LAUNCH
+#undef A1_STAGED
 
 void a1mpc_default_tick_params(a1mpc_tick_params* p) {
     if (!p) return;
@@ -2398,59 +2339,33 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
     A1_HIP(hipSetDevice(h->device));
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
     A1_ORDER(h, s);
-    const size_t N = n;
     if (!h->d_tickrec) A1_HIP(hipMalloc(&h->d_tickrec, (static_cast<size_t>(h->max_batch) * 22 + 3) * sizeof(double)));
     if (pv_sched && !h->d_pv_sched) A1_HIP(hipMalloc(&h->d_pv_sched, static_cast<size_t>(h->max_batch) * h->cfg.horizon * sizeof(uint32_t)));
     if (pv_feet && !h->d_pv_foot) A1_HIP(hipMalloc(&h->d_pv_foot, static_cast<size_t>(h->max_batch) * 12 * h->cfg.horizon * sizeof(double)));
-    if (!h->d_ekf_state) {
-        A1_HIP(hipMalloc(&h->d_ekf_state, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double)));
-        A1_HIP(hipMemsetAsync(h->d_ekf_state, 0, static_cast<size_t>(h->max_batch) * kEkfState * sizeof(double), s));
-    }
+    if (a1mpc_status st = ensure_ekf_state(h, s); st != A1MPC_OK) return st;
     if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
     if (!h->timing && (tick_markers() & 2)) A1_HIP(hipEventRecord(h->ev_mark, s));
     if (h->timing) A1_HIP(hipEventRecord(h->ev_tick0, s));   // (ev_tick0 .. ev_tick1 = the whole tick; ev0 .. ev1 = the MPC launch, as after every solve)
-    {   // 1. leg state (uses the previous estimate of root_pos / root_lin_vel for the world-frame outputs, like the reference's callback)
-        LegArgs a;
-        a.n = n;
-        std::memcpy(a.rho_fix, p->rho_fix, sizeof a.rho_fix); std::memcpy(a.rho_opt, p->rho_opt, sizeof a.rho_opt);
-        a.q = bf->joint_pos; a.qd = bf->joint_vel; a.R = bf->R_world; a.pos = bf->root_pos; a.vel = bf->root_lin_vel; a.rel = bf->foot_pos_rel; a.Jb = bf->j_foot_blocks;
-        a.vrel = bf->foot_vel_rel; a.pabs = bf->foot_pos_abs; a.vabs = bf->foot_vel_abs; a.pworld = bf->foot_pos_world; a.vworld = bf->foot_vel_world;
-        hipLaunchKernelGGL(a1mpc_leg_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
-    }
-    {   // 2. EKF
-        EkfArgs a;
-        a.n = n; a.dt = p->control_dt; a.flat = p->assume_flat_ground; a.state = h->d_ekf_state; a.mode = bf->movement_mode; a.ff = bf->foot_force; a.R = bf->R_world;
-        a.acc = bf->imu_acc; a.w = bf->imu_ang_vel; a.fk = bf->foot_pos_rel; a.fv = bf->foot_vel_rel; a.pos_out = bf->root_pos; a.vel_out = bf->root_lin_vel;
-        a.ec_out = bf->estimated_contacts;
-        if (n > h->ekf_ready_n) {   // (robots 0 .. ekf_ready_n - 1 have been through init_state: nothing for the init kernel to do -- one launch less per tick)
-            hipLaunchKernelGGL(a1mpc_ekf_init_kernel, dim3(static_cast<unsigned>((N + 255) / 256)), dim3(256), 0, s, a);
-            if (hipError_t ei = hipGetLastError(); ei != hipSuccess) { h->ekf_ready_n = 0; return fail(A1MPC_ERR_HIP, std::string("a1mpc_ekf_init_kernel: ") + hipGetErrorString(ei)); }
-            h->ekf_ready_n = n;
-        }
-        launch_ekf_update(a, s);
-    }
-    {   // 3. update_plan + 4. swing legs, one launch (a1mpc_plan_swing_kernel).  (Round 5 trial: the swing block as its own launch on a second stream beside stage 5 --
-        //    both only need the plan's outputs -- joined in front of the MPC launch: the two cross-stream event waits cost more than the 5 us kernel they hide,
-        //    0.490 -> 0.503 ms per tick at 4096 robots; profiles/r05_control_tick.txt)
-        PlanArgs a;
-        a.g = p->gait; a.n = n; a.movement_mode = bf->movement_mode; a.gait_counter = bf->gait_counter; a.gait_counter_speed = bf->gait_counter_speed;
-        a.root_lin_vel = bf->root_lin_vel; a.Rz = bf->R_z; a.Rw = bf->R_world; a.root_pos = bf->root_pos; a.root_lin_vel_d = bf->root_lin_vel_d;
-        a.plan_contacts = bf->plan_contacts; a.rel = bf->foot_pos_target_rel; a.abs_ = bf->foot_pos_target_abs; a.world = bf->foot_pos_target_world;
-        SwingArgs w;
-        w.n = n; w.counter_per_swing = p->gait.counter_per_swing; w.dt = p->control_dt;
-        for (int k = 0; k < 3; ++k) { w.kp[k] = p->kp_foot[k]; w.kd[k] = p->kd_foot[k]; }
-        w.Rz = bf->R_z; w.foot_pos_abs = bf->foot_pos_abs; w.gait_counter = bf->gait_counter; w.target_rel = bf->foot_pos_target_rel; w.start = bf->foot_pos_start;
-        w.rel_last = bf->foot_pos_rel_last_time; w.target_last = bf->foot_pos_target_last_time; w.cur_out = bf->foot_pos_cur; w.kin_out = bf->foot_forces_kin;
-        hipLaunchKernelGGL(a1mpc_plan_swing_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a, w);
-    }
+    // 1. leg state (uses the previous estimate of root_pos / root_lin_vel for the world-frame outputs, like the reference's callback)
+    launch_leg(n, p->rho_fix, p->rho_opt, bf->joint_pos, bf->joint_vel, bf->R_world, bf->root_pos, bf->root_lin_vel, bf->foot_pos_rel, bf->j_foot_blocks, bf->foot_vel_rel,
+               bf->foot_pos_abs, bf->foot_vel_abs, bf->foot_pos_world, bf->foot_vel_world, s);
+    // 2. EKF
+    A1_LAUNCH_EKF(h, n, p->control_dt, p->assume_flat_ground, bf->movement_mode, bf->foot_force, bf->R_world, bf->imu_acc, bf->imu_ang_vel, bf->foot_pos_rel, bf->foot_vel_rel,
+                  bf->root_pos, bf->root_lin_vel, bf->estimated_contacts, s);
+    // 3. update_plan + 4. swing legs, one launch (a1mpc_plan_swing_kernel).  (Round 5 trial: the swing block as its own launch on a second stream beside stage 5 --
+    //    both only need the plan's outputs -- joined in front of the MPC launch: the two cross-stream event waits cost more than the 5 us kernel they hide,
+    //    0.490 -> 0.503 ms per tick at 4096 robots; profiles/r05_control_tick.txt)
+    hipLaunchKernelGGL(a1mpc_plan_swing_kernel, leg_lane_grid(n), dim3(256), 0, s,
+                       make_plan_args(p->gait, n, bf->movement_mode, bf->gait_counter, bf->gait_counter_speed, bf->root_lin_vel, bf->R_z, bf->R_world, bf->root_pos, bf->root_lin_vel_d,
+                                      bf->plan_contacts, bf->foot_pos_target_rel, bf->foot_pos_target_abs, bf->foot_pos_target_world),
+                       make_swing_args(n, p->gait.counter_per_swing, p->control_dt, p->kp_foot, p->kd_foot, bf->R_z, bf->foot_pos_abs, bf->gait_counter, bf->foot_pos_target_rel,
+                                       bf->foot_pos_start, bf->foot_pos_rel_last_time, bf->foot_pos_target_last_time, bf->foot_pos_cur, bf->foot_forces_kin));
     {   // 5. contacts / terrain: root_pos[2] and root_euler_d[1] are read / written in place (strides of 3); 6. the tick record, by the same lanes
-        ContactArgs a;
-        a.recent_in = nullptr; a.z_stride = 3; a.pitch_stride = 3;
+        ContactArgs a = make_contact_args(h, p->contact, n, bf->gait_counter, bf->plan_contacts, bf->foot_force, bf->foot_pos_abs, bf->root_pos + 2, bf->root_euler_d + 1, bf->contacts,
+                                          bf->foot_pos_recent_contact, bf->terrain_angle);
+        a.z_stride = 3; a.pitch_stride = 3;
         a.pk_euler = bf->root_euler; a.pk_pos = bf->root_pos; a.pk_ang_vel = bf->root_ang_vel; a.pk_lin_vel = bf->root_lin_vel; a.pk_euler_d = bf->root_euler_d;
         a.pk_lin_vel_d = bf->root_lin_vel_d; a.pk_ang_vel_d = bf->root_ang_vel_d; a.pk_pos_d_z = bf->root_pos_d_z; a.pk_tick = h->d_tickrec;
-        a.n = n; a.counter_per_swing = p->contact.counter_per_swing; a.foot_force_low = p->contact.foot_force_low; a.use_terrain_adapt = p->contact.use_terrain_adapt;
-        contact_state_pointers(h, a); a.gait_counter = bf->gait_counter; a.foot_force = bf->foot_force; a.foot_pos_abs = bf->foot_pos_abs; a.root_pos_z = bf->root_pos + 2;
-        a.plan_contacts = bf->plan_contacts; a.pitch_d = bf->root_euler_d + 1; a.contacts = bf->contacts; a.recent_out = bf->foot_pos_recent_contact; a.terrain_out = bf->terrain_angle;
         launch_contact_terrain(a, s);
     }
     A1_HIP(hipGetLastError());
@@ -2477,10 +2392,7 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
                                             pv_sched ? 4 : 0, nullptr, &tq);
         st != A1MPC_OK) return st;
     if (!tq.fused) {   // the split pipeline solved this tick (a first tick, a batch beyond the fused kernel's range): N3 as its own launch
-        TorqueArgs a;
-        a.n = n; a.active = bf->mpc_active; a.contacts = bf->contacts; a.Jb = bf->j_foot_blocks; a.grf = bf->grf; a.fkin = bf->foot_forces_kin; a.tg = bf->torques_gravity; a.tau = bf->joint_torques;
-        a.km[0] = p->km_foot[0]; a.km[1] = p->km_foot[1]; a.km[2] = p->km_foot[2];
-        hipLaunchKernelGGL(a1mpc_torque_kernel, dim3(static_cast<unsigned>((N * 4 + 255) / 256)), dim3(256), 0, s, a);
+        launch_torque(n, bf->mpc_active, bf->contacts, bf->j_foot_blocks, bf->grf, bf->foot_forces_kin, p->km_foot, bf->torques_gravity, bf->joint_torques, s);
         A1_HIP(hipGetLastError());
     }
     h->tick_fused = tq.fused;
@@ -2489,6 +2401,7 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
     A1_MARK(h, s);
     return A1MPC_OK;
 }
+#undef A1_LAUNCH_EKF
 a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
     return control_tick_impl(h, p, nullptr, bf, n, hip_stream);
 }
@@ -2674,37 +2587,6 @@ a1mpc_status a1mpc_solve_batch(a1mpc_handle h, int32_t n, const double* x0, cons
     if (a1mpc_status st = host_submit(h, n, x0, x_ref, R_world, foot_abs, contact, u_full_out != nullptr, &armed); st != A1MPC_OK) return st;
     if (a1mpc_status st = wait_outputs(h, n, armed, "a1mpc_solve_batch"); st != A1MPC_OK) return st;
     host_collect(h, n, 12 * h->cfg.horizon, grf_body_out, u_full_out, iters_out, status_out);
-    return A1MPC_OK;
-}
-
-// ---- terrain block of compute_grf alone (S/A1RobotControl.cpp:335-376 + compute_walking_surface :566-582): foot_pos_recent_contact comes from
-// the caller's A1CtrlStates (the reference fills it in generate_swing_legs_ctrl); the terrain-angle filter of every robot lives in the handle
-a1mpc_status a1mpc_terrain_batch(a1mpc_handle h, int32_t use_terrain_adapt, int32_t n, const double* foot_pos_recent_contact, const double* root_pos_z,
-                                 double* root_euler_d_pitch, double* terrain_angle_out) {
-    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || !foot_pos_recent_contact || !root_pos_z || !root_euler_d_pitch || !terrain_angle_out) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
-    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
-    if (n == 0) return A1MPC_OK;
-    A1_HIP(hipSetDevice(h->device));
-    if (a1mpc_status st = ensure_aux(h); st != A1MPC_OK) return st;
-    const size_t N = n;
-    hipStream_t s = h->stream;
-    A1_ORDER(h, s);
-    if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
-    double *d_rec = h->d_aux_in, *d_z = d_rec + 12 * N, *d_pd = d_z + N, *d_ta = h->d_aux_out;
-    A1_HIP(hipMemcpyAsync(d_rec, foot_pos_recent_contact, N * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_z, root_pos_z, N * sizeof(double), hipMemcpyHostToDevice, s));
-    A1_HIP(hipMemcpyAsync(d_pd, root_euler_d_pitch, N * sizeof(double), hipMemcpyHostToDevice, s));
-    ContactArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n = n; a.use_terrain_adapt = use_terrain_adapt; contact_state_pointers(h, a); a.root_pos_z = d_z; a.pitch_d = d_pd; a.z_stride = 1; a.pitch_stride = 1; a.pk_tick = nullptr;
-    a.recent_in = d_rec; a.recent_out = nullptr; a.terrain_out = d_ta;
-    launch_contact_terrain(a, s);
-    A1_HIP(hipGetLastError());
-    A1_MARK(h, s);
-    A1_HIP(hipMemcpyAsync(terrain_angle_out, d_ta, N * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipMemcpyAsync(root_euler_d_pitch, d_pd, N * sizeof(double), hipMemcpyDeviceToHost, s));
-    A1_HIP(hipStreamSynchronize(s));
     return A1MPC_OK;
 }
 
