@@ -272,6 +272,8 @@ __global__ __launch_bounds__(256) void a1mpc_plan_kernel(const PlanArgs a) {
 //             will, so step t IS the plan_contacts of t * ticks_per_step ticks from now -- and keeps the H contact bits in one register; the four lanes of a robot
 //             exchange their registers and lane `leg` stores steps leg, leg + 4, ... as whole 4-byte words (the robot's four lanes: 16 consecutive bytes per store)
 //   feet      f_0 = foot_pos_abs, f_(t+1) = f_t - (v * dt): the product is rounded first, then subtracted; v = root_lin_vel_d (mode 1) or R_world * root_lin_vel_d (mode 2)
+//   footholds the sibling kernel: where the lane's contact bits show a touchdown (bit t set, bit t - 1 clear, t >= 1) f_t is the leg's foot_pos_target_abs of this tick,
+//             update_plan's Raibert foothold (S/A1RobotControl.cpp:166-199), and the recurrence continues from it
 struct PreviewArgs {
     int32_t n, H, ticks_per_step;
     int32_t sched_mode;   // 0: contacts[] at every step (the reference's broadcast written out), 1: the gait's schedule
@@ -281,61 +283,89 @@ struct PreviewArgs {
     const double *gait_counter, *gait_counter_speed, *foot_pos_abs, *Rw, *root_lin_vel_d;
     uint32_t* sched;      // n x H words (4 contact bytes each), or null
     double* foot_steps;   // n x 12H, or null
+    const double* foot_target_abs;   // n x 12, this tick's Raibert footholds (a1mpc_horizon_preview_footholds_kernel), or null: the feet are the recurrence alone
 };
-__global__ __launch_bounds__(256) void a1mpc_horizon_preview_kernel(const PreviewArgs a) {
+// bit t: leg `leg` of robot b is in contact at horizon step t
+__device__ __forceinline__ uint32_t preview_contact_bits(const PreviewArgs& a, int64_t b, int leg, int H) {
 #pragma clang fp contract(off)
+    const uint32_t all = (1u << H) - 1u;   // (H <= 20)
+    const uint32_t c0 = a.contacts[b * 4 + leg] ? 1u : 0u;   // step 0: the actual contacts[] (S/A1RobotControl.cpp:271), the value the reference broadcasts
+    if (a.sched_mode == 0) return c0 ? all : 0u;
+    if (!a.movement_mode[b]) return c0 | (all & ~1u);   // stand: every planned contact is 1 (:150-153)
+    double c = a.gait_counter[b * 4 + leg];
+    const double spd = a.gait_counter_speed[b * 4 + leg];
+    uint32_t m = c0;
+    for (int t = 1; t < H; ++t) {
+        for (int k = 0; k < a.ticks_per_step; ++k) {   // :158-159, one control tick
+            c = c + spd;
+            c = fmod(c, a.counter_per_gait);
+        }
+        m |= (c <= a.counter_per_swing ? 1u : 0u) << t;   // :160-164
+    }
+    return m;
+}
+// the four lanes of a robot exchange their registers; lane `leg` stores steps leg, leg + 4, ...  (every lane of the wavefront takes part in the exchange: no lane has left)
+__device__ __forceinline__ void preview_store_sched(const PreviewArgs& a, uint32_t m, int lane, bool live, int64_t b, int leg, int H) {
+    const int q0 = lane & ~3;
+    const uint32_t m0 = __shfl(m, q0, 64), m1 = __shfl(m, q0 + 1, 64), m2 = __shfl(m, q0 + 2, 64), m3 = __shfl(m, q0 + 3, 64);
+    if (live) {
+        uint32_t* out = a.sched + b * H;
+        for (int t = leg; t < H; t += 4)
+            out[t] = ((m0 >> t) & 1u) | (((m1 >> t) & 1u) << 8) | (((m2 >> t) & 1u) << 16) | (((m3 >> t) & 1u) << 24);
+    }
+}
+// the feet of one (robot, leg).  kFootholds: at a touchdown -- contact bit t set, bit t - 1 clear -- the foot is this tick's foot_pos_target_abs, the words copied, and the
+// recurrence goes on from there (a second touchdown inside the horizon is the same target again)
+template <bool kFootholds>
+__device__ __forceinline__ void preview_feet(const PreviewArgs& a, int64_t b, int leg, int H, uint32_t m) {
+#pragma clang fp contract(off)
+    const double* vd = a.root_lin_vel_d + b * 3;
+    double v[3] = {vd[0], vd[1], vd[2]};
+    if (a.foot_mode == 2) {   // root_lin_vel_d_world = root_rot_mat * root_lin_vel_d (S/A1RobotControl.cpp:470)
+        const double* R = a.Rw + b * 9;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) v[r] = R[r * 3 + 0] * vd[0] + R[r * 3 + 1] * vd[1] + R[r * 3 + 2] * vd[2];
+    }
+    const double* f0 = a.foot_pos_abs + b * 12 + 3 * leg;
+    double f[3] = {f0[0], f0[1], f0[2]};
+    const double st[3] = {v[0] * a.dt, v[1] * a.dt, v[2] * a.dt};   // root_lin_vel_d * dt: the same product at every step
+    double T[3] = {0.0, 0.0, 0.0};
+    uint32_t land = 0;   // bit t: a touchdown at step t >= 1
+    if (kFootholds) {
+        const double* tg = a.foot_target_abs + b * 12 + 3 * leg;   // S/A1RobotControl.cpp:198, update_plan's third output
+        T[0] = tg[0]; T[1] = tg[1]; T[2] = tg[2];
+        land = m & ~(m << 1) & ~1u;
+    }
+    double* out = a.foot_steps + b * 12 * H + 3 * leg;
+    for (int t = 0; t < H; ++t) {
+        if (kFootholds && ((land >> t) & 1u)) { f[0] = T[0]; f[1] = T[1]; f[2] = T[2]; }
+        out[0] = f[0]; out[1] = f[1]; out[2] = f[2];
+        f[0] = f[0] - st[0]; f[1] = f[1] - st[1]; f[2] = f[2] - st[2];   // S/test/test_mpc.cpp:112-115
+        out += 12;
+    }
+}
+__global__ __launch_bounds__(256) void a1mpc_horizon_preview_kernel(const PreviewArgs a) {
     const int lane = static_cast<int>(threadIdx.x) & 63;
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     const int64_t b = gid >> 2;
     const int leg = static_cast<int>(gid & 3);
     const bool live = b < a.n;
     const int H = a.H;
-    if (a.sched != nullptr) {
-        uint32_t m = 0;   // bit t: my leg is in contact at horizon step t
-        if (live) {
-            const uint32_t all = (1u << H) - 1u;   // (H <= 20)
-            const uint32_t c0 = a.contacts[b * 4 + leg] ? 1u : 0u;   // step 0: the actual contacts[] (S/A1RobotControl.cpp:271), the value the reference broadcasts
-            if (a.sched_mode == 0) m = c0 ? all : 0u;
-            else if (!a.movement_mode[b]) m = c0 | (all & ~1u);   // stand: every planned contact is 1 (:150-153)
-            else {
-                double c = a.gait_counter[b * 4 + leg];
-                const double spd = a.gait_counter_speed[b * 4 + leg];
-                m = c0;
-                for (int t = 1; t < H; ++t) {
-                    for (int k = 0; k < a.ticks_per_step; ++k) {   // :158-159, one control tick
-                        c = c + spd;
-                        c = fmod(c, a.counter_per_gait);
-                    }
-                    m |= (c <= a.counter_per_swing ? 1u : 0u) << t;   // :160-164
-                }
-            }
-        }
-        const int q0 = lane & ~3;   // (every lane of the wavefront takes part in the exchange: no lane has left)
-        const uint32_t m0 = __shfl(m, q0, 64), m1 = __shfl(m, q0 + 1, 64), m2 = __shfl(m, q0 + 2, 64), m3 = __shfl(m, q0 + 3, 64);
-        if (live) {
-            uint32_t* out = a.sched + b * H;
-            for (int t = leg; t < H; t += 4)
-                out[t] = ((m0 >> t) & 1u) | (((m1 >> t) & 1u) << 8) | (((m2 >> t) & 1u) << 16) | (((m3 >> t) & 1u) << 24);
-        }
-    }
-    if (a.foot_steps != nullptr && live) {
-        const double* vd = a.root_lin_vel_d + b * 3;
-        double v[3] = {vd[0], vd[1], vd[2]};
-        if (a.foot_mode == 2) {   // root_lin_vel_d_world = root_rot_mat * root_lin_vel_d (S/A1RobotControl.cpp:470)
-            const double* R = a.Rw + b * 9;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) v[r] = R[r * 3 + 0] * vd[0] + R[r * 3 + 1] * vd[1] + R[r * 3 + 2] * vd[2];
-        }
-        const double* f0 = a.foot_pos_abs + b * 12 + 3 * leg;
-        double f[3] = {f0[0], f0[1], f0[2]};
-        const double st[3] = {v[0] * a.dt, v[1] * a.dt, v[2] * a.dt};   // root_lin_vel_d * dt: the same product at every step
-        double* out = a.foot_steps + b * 12 * H + 3 * leg;
-        for (int t = 0; t < H; ++t) {
-            out[0] = f[0]; out[1] = f[1]; out[2] = f[2];
-            f[0] = f[0] - st[0]; f[1] = f[1] - st[1]; f[2] = f[2] - st[2];   // S/test/test_mpc.cpp:112-115
-            out += 12;
-        }
-    }
+    if (a.sched != nullptr) preview_store_sched(a, live ? preview_contact_bits(a, b, leg, H) : 0u, lane, live, b, leg, H);
+    if (a.foot_steps != nullptr && live) preview_feet<false>(a, b, leg, H, 0u);
+}
+// ... with footholds (a1mpc_horizon_preview_footholds_batch, foot_steps and foot_target_abs non-null, sched_mode 1): the lane's contact bits are computed whether or
+// not the schedule is an output, because the feet read them
+__global__ __launch_bounds__(256) void a1mpc_horizon_preview_footholds_kernel(const PreviewArgs a) {
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const int64_t b = gid >> 2;
+    const int leg = static_cast<int>(gid & 3);
+    const bool live = b < a.n;
+    const int H = a.H;
+    const uint32_t m = live ? preview_contact_bits(a, b, leg, H) : 0u;
+    if (a.sched != nullptr) preview_store_sched(a, m, lane, live, b, leg, H);
+    if (live) preview_feet<true>(a, b, leg, H, m);
 }
 
 thread_local std::string g_last_error;
@@ -2233,14 +2263,17 @@ static const char* invalid_preview(a1mpc_handle h, const a1mpc_preview_config* p
 // the launch alone (arguments validated by the caller, which also orders and marks the stream)
 static void launch_preview(a1mpc_handle h, const a1mpc_preview_config& pv, double counter_per_gait, double counter_per_swing, int32_t n, const uint8_t* movement_mode,
                            const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs, const double* R_world,
-                           const double* root_lin_vel_d, uint8_t* sched_out, double* foot_steps_out, hipStream_t s) {
+                           const double* root_lin_vel_d, uint8_t* sched_out, double* foot_steps_out, hipStream_t s, const double* foot_target_abs = nullptr) {
     PreviewArgs a;
     a.n = n; a.H = h->cfg.horizon; a.ticks_per_step = pv.ticks_per_step; a.sched_mode = pv.contact_schedule; a.foot_mode = pv.foot_preview;
     a.counter_per_gait = counter_per_gait; a.counter_per_swing = counter_per_swing; a.dt = h->cfg.dt;
     a.movement_mode = movement_mode; a.contacts = contacts; a.gait_counter = gait_counter; a.gait_counter_speed = gait_counter_speed;
     a.foot_pos_abs = foot_pos_abs; a.Rw = R_world; a.root_lin_vel_d = root_lin_vel_d;
     a.sched = reinterpret_cast<uint32_t*>(sched_out); a.foot_steps = foot_steps_out;
-    hipLaunchKernelGGL(a1mpc_horizon_preview_kernel, leg_lane_grid(n), dim3(256), 0, s, a);
+    // the footholds replace a foot only at a touchdown, and only a schedule has one: without target, feet or schedule the existing kernel IS the rule
+    a.foot_target_abs = foot_steps_out != nullptr && pv.contact_schedule == 1 ? foot_target_abs : nullptr;
+    if (a.foot_target_abs) hipLaunchKernelGGL(a1mpc_horizon_preview_footholds_kernel, leg_lane_grid(n), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(a1mpc_horizon_preview_kernel, leg_lane_grid(n), dim3(256), 0, s, a);
 }
 // pointer rules shared by the two preview entries: each output needs its inputs
 static const char* invalid_preview_io(const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, const uint8_t* movement_mode, const double* gait_counter,
@@ -2255,18 +2288,49 @@ static const char* invalid_preview_io(const a1mpc_preview_config* pv, const a1mp
     if (device && (reinterpret_cast<uintptr_t>(sched_out) & 3u)) return "contact_sched_out must be 4-byte aligned (it is written one horizon step, four contact bytes, at a time)";
     return nullptr;
 }
-a1mpc_status a1mpc_horizon_preview_batch_device(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n,
-                                                const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts,
-                                                const double* foot_pos_abs, const double* R_world, const double* root_lin_vel_d, uint8_t* sched_out,
-                                                double* foot_steps_out, void* hip_stream) {
+// what the foothold entries refuse beyond invalid_preview_io, or null: feet without their target, and -- the footholds read the schedule -- feet under contact_schedule 1
+// without the schedule's inputs, whether or not the schedule itself is an output
+static const char* invalid_footholds_io(const a1mpc_preview_config* pv, const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed,
+                                        const uint8_t* contacts, const double* foot_pos_target_abs, const double* foot_steps_out) {
+    if (!foot_steps_out) return nullptr;
+    if (!foot_pos_target_abs) return "foot_steps_out needs foot_pos_target_abs (null)";
+    if (pv->contact_schedule != 1) return nullptr;
+    if (!movement_mode) return "null movement_mode: the footholds read the schedule (contact_schedule 1)";
+    if (!gait_counter) return "null gait_counter: the footholds read the schedule (contact_schedule 1)";
+    if (!gait_counter_speed) return "null gait_counter_speed: the footholds read the schedule (contact_schedule 1)";
+    if (!contacts) return "null contacts: the footholds read the schedule (contact_schedule 1)";
+    return nullptr;
+}
+static a1mpc_status preview_device_impl(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
+                                        const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs,
+                                        const double* R_world, const double* root_lin_vel_d, bool footholds, const double* foot_pos_target_abs, uint8_t* sched_out,
+                                        double* foot_steps_out, void* hip_stream) {
     if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
     if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
     if (const char* bad = invalid_preview_io(pv, gait, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, sched_out, foot_steps_out, true))
         return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (footholds)
+        if (const char* bad = invalid_footholds_io(pv, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_target_abs, foot_steps_out))
+            return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
     A1_STAGE_DEVICE(hip_stream);
     A1_STAGE_LAUNCH(launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world,
-                                   root_lin_vel_d, sched_out, foot_steps_out, s));
+                                   root_lin_vel_d, sched_out, foot_steps_out, s, footholds ? foot_pos_target_abs : nullptr));
     return A1MPC_OK;
+}
+a1mpc_status a1mpc_horizon_preview_batch_device(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n,
+                                                const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts,
+                                                const double* foot_pos_abs, const double* R_world, const double* root_lin_vel_d, uint8_t* sched_out,
+                                                double* foot_steps_out, void* hip_stream) {
+    return preview_device_impl(h, pv, gait, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, false, nullptr, sched_out,
+                               foot_steps_out, hip_stream);
+}
+// a1mpc_horizon_preview_batch_device with the foothold rule: a leg that the schedule puts down inside the horizon stands at foot_pos_target_abs from that step on
+a1mpc_status a1mpc_horizon_preview_footholds_batch_device(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n,
+                                                          const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed,
+                                                          const uint8_t* contacts, const double* foot_pos_abs, const double* R_world, const double* root_lin_vel_d,
+                                                          const double* foot_pos_target_abs, uint8_t* sched_out, double* foot_steps_out, void* hip_stream) {
+    return preview_device_impl(h, pv, gait, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, true, foot_pos_target_abs,
+                               sched_out, foot_steps_out, hip_stream);
 }
 // the handle's per-step staging (a1mpc_solve_batch_strided's too): n x 12H feet, n x 4H contact bytes
 static a1mpc_status ensure_step_staging(a1mpc_handle h) {
@@ -2276,26 +2340,45 @@ static a1mpc_status ensure_step_staging(a1mpc_handle h) {
     A1_HIP(hipMalloc(&h->d_contact_steps, static_cast<size_t>(h->max_batch) * 4 * H));
     return A1MPC_OK;
 }
-a1mpc_status a1mpc_horizon_preview_batch(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
-                                         const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs,
-                                         const double* R_world, const double* root_lin_vel_d, uint8_t* sched_out, double* foot_steps_out) {
+static a1mpc_status preview_host_impl(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
+                                      const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs,
+                                      const double* R_world, const double* root_lin_vel_d, bool footholds, const double* foot_pos_target_abs, uint8_t* sched_out,
+                                      double* foot_steps_out) {
     if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
     if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
     if (const char* bad = invalid_preview_io(pv, gait, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, sched_out, foot_steps_out,
                                              false)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);   // (a host array for the schedule may sit at any address: it is staged)
+    if (footholds)
+        if (const char* bad = invalid_footholds_io(pv, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_target_abs, foot_steps_out))
+            return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    const bool with_target = footholds && foot_steps_out != nullptr;   // (without feet to produce the call IS the existing entry: the target is not read, not even staged)
     A1_STAGE_DEVICE(nullptr);
     Staging sg(h, n, s);
     if (a1mpc_status st = ensure_step_staging(h); st != A1MPC_OK) return st;
     // (an input that the configured preview does not read may be null: its slice is handed to the kernel unfilled.)  Out: the handle's per-step buffers
     const double *d_gc = sg.in(gait_counter, 4), *d_spd = sg.in(gait_counter_speed, 4), *d_fp = sg.in(foot_pos_abs, 12), *d_R = sg.in(R_world, 9), *d_vd = sg.in(root_lin_vel_d, 3);
     const uint8_t *d_mm = sg.in(movement_mode, 1), *d_ct = sg.in(contacts, 4);
+    const double* d_tg = with_target ? sg.in(foot_pos_target_abs, 12) : nullptr;
     const size_t H = h->cfg.horizon;
     sg.back(sched_out, h->d_contact_steps, 4 * H);
     sg.back(foot_steps_out, h->d_foot_steps, 12 * H);
     A1_STAGED(sg);
     A1_STAGE_LAUNCH(launch_preview(h, *pv, gait->counter_per_gait, gait->counter_per_swing, n, d_mm, d_gc, d_spd, d_ct, d_fp, d_R, d_vd, sched_out ? h->d_contact_steps : nullptr,
-                                   foot_steps_out ? h->d_foot_steps : nullptr, s));
+                                   foot_steps_out ? h->d_foot_steps : nullptr, s, d_tg));
     return sg.finish();
+}
+a1mpc_status a1mpc_horizon_preview_batch(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
+                                         const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs,
+                                         const double* R_world, const double* root_lin_vel_d, uint8_t* sched_out, double* foot_steps_out) {
+    return preview_host_impl(h, pv, gait, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, false, nullptr, sched_out,
+                             foot_steps_out);
+}
+a1mpc_status a1mpc_horizon_preview_footholds_batch(a1mpc_handle h, const a1mpc_preview_config* pv, const a1mpc_gait_config* gait, int32_t n, const uint8_t* movement_mode,
+                                                   const double* gait_counter, const double* gait_counter_speed, const uint8_t* contacts, const double* foot_pos_abs,
+                                                   const double* R_world, const double* root_lin_vel_d, const double* foot_pos_target_abs, uint8_t* sched_out,
+                                                   double* foot_steps_out) {
+    return preview_host_impl(h, pv, gait, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, true, foot_pos_target_abs,
+                             sched_out, foot_steps_out);
 }
 #undef A1_STAGE_BEGIN
 #undef A1_STAGE_DEVICE
@@ -2321,7 +2404,8 @@ void a1mpc_default_tick_params(a1mpc_tick_params* p) {
 // pack and the MPC launch back to back on one stream, no host round trip, and N3 inside the MPC kernel's output stage whenever the tick runs the fused / latency kernel
 // (every warm-started tick of a known batch).  Bit-identical to chaining the seven *_device entry points.
 // pv: the gait-aware horizon (a1mpc_control_tick_preview_device), or null / {0, 0, *}: the plain tick -- the same launches as before the preview existed
-static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
+static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream,
+                                      bool footholds = false) {
     if (!h || !p || !bf) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle / params / buffers");
     const bool pv_sched = pv != nullptr && pv->contact_schedule == 1, pv_feet = pv != nullptr && pv->foot_preview != 0;
     if ((pv_sched || pv_feet) && !(p->gait.counter_per_gait > 0)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "a1mpc_gait_config.counter_per_gait <= 0");
@@ -2334,6 +2418,8 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
                           bf->plan_contacts, bf->contacts, bf->foot_pos_rel, bf->j_foot_blocks, bf->foot_vel_rel, bf->foot_pos_abs, bf->foot_pos_target_rel, bf->foot_pos_cur,
                           bf->foot_forces_kin, bf->foot_pos_recent_contact, bf->terrain_angle, bf->grf};
     for (const void* q : need) if (!q) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null device pointer in a1mpc_tick_buffers (only the optional outputs may be null)");
+    if (footholds && pv_feet && !bf->foot_pos_target_abs)
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null a1mpc_tick_buffers.foot_pos_target_abs: the foothold preview reads it (foot_preview != 0)");
     if (!(p->control_dt > 0)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "control_dt <= 0");
     if (n == 0) return A1MPC_OK;
     A1_HIP(hipSetDevice(h->device));
@@ -2380,7 +2466,8 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
     const double* mpc_foot = bf->foot_pos_abs; const uint8_t* mpc_contact = bf->contacts;
     if (pv_sched || pv_feet) {
         launch_preview(h, *pv, p->gait.counter_per_gait, p->gait.counter_per_swing, n, bf->movement_mode, bf->gait_counter, bf->gait_counter_speed, bf->contacts, bf->foot_pos_abs,
-                       bf->R_world, bf->root_lin_vel_d, pv_sched ? reinterpret_cast<uint8_t*>(h->d_pv_sched) : nullptr, pv_feet ? h->d_pv_foot : nullptr, s);
+                       bf->R_world, bf->root_lin_vel_d, pv_sched ? reinterpret_cast<uint8_t*>(h->d_pv_sched) : nullptr, pv_feet ? h->d_pv_foot : nullptr, s,
+                       footholds ? bf->foot_pos_target_abs : nullptr);   // (stage 3 of this tick wrote it)
         A1_HIP(hipGetLastError());
         if (pv_sched) mpc_contact = reinterpret_cast<const uint8_t*>(h->d_pv_sched);
         if (pv_feet) mpc_foot = h->d_pv_foot;
@@ -2409,6 +2496,12 @@ a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* 
 a1mpc_status a1mpc_control_tick_preview_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
     if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
     return control_tick_impl(h, p, pv, bf, n, hip_stream);
+}
+// ... with the feet of a leg that lands inside the horizon at this tick's Raibert foothold, buffers->foot_pos_target_abs; foot_preview 0 IS a1mpc_control_tick_preview_device
+a1mpc_status a1mpc_control_tick_preview_footholds_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n,
+                                                         void* hip_stream) {
+    if (const char* bad = invalid_preview(h, pv)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    return control_tick_impl(h, p, pv, bf, n, hip_stream, true);
 }
 a1mpc_status a1mpc_last_control_tick_ms(a1mpc_handle h, float* ms_out, int32_t* torques_fused_out) {
     if (!h || !ms_out) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle/out");
@@ -3353,6 +3446,15 @@ a1mpc_status a1mpc_pipeline_submit_ticks_device(a1mpc_pipeline p, int32_t slot, 
     if (!d_tick) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
     return pipeline_submit_device_impl(p, slot, fresh_batch, n, d_tick, nullptr, nullptr, d_R_world, d_foot_abs, 0, d_contact, 0, nullptr, d_grf_body_out,
                                        d_u_full_out, d_iters_out, d_status_out, inputs_ready_stream, slot_out);
+}
+// the tick-record submit with the strides let through, as a1mpc_solve_batch_ticks_strided_device is on a lone handle: (0, 0, NULL) IS a1mpc_pipeline_submit_ticks_device
+a1mpc_status a1mpc_pipeline_submit_ticks_strided_device(a1mpc_pipeline p, int32_t slot, int32_t fresh_batch, int32_t n, const double* d_tick, const double* d_R_world,
+                                                        const double* d_foot_abs, int32_t foot_stride, const uint8_t* d_contact, int32_t contact_stride,
+                                                        const double* d_yaw_A, double* d_grf_body_out, double* d_u_full_out, int32_t* d_iters_out, int32_t* d_status_out,
+                                                        void* inputs_ready_stream, int32_t* slot_out) {
+    if (!d_tick) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
+    return pipeline_submit_device_impl(p, slot, fresh_batch, n, d_tick, nullptr, nullptr, d_R_world, d_foot_abs, foot_stride, d_contact, contact_stride, d_yaw_A,
+                                       d_grf_body_out, d_u_full_out, d_iters_out, d_status_out, inputs_ready_stream, slot_out);
 }
 // ... and host arrays in / out (what a caller on the reference's side of the boundary holds): snapshot + launches queued on the slot's stream, outputs handed over by
 // a1mpc_pipeline_wait / the next submit to the slot

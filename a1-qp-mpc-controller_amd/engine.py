@@ -60,7 +60,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_preview_config", "a1mpc_horizon_preview_batch", "a1mpc_horizon_preview_batch_device", "a1mpc_solve_batch_ticks_strided", "a1mpc_solve_batch_ticks_strided_device",
+EXPORTS = ["a1mpc_horizon_preview_footholds_batch", "a1mpc_horizon_preview_footholds_batch_device", "a1mpc_control_tick_preview_footholds_device",
+           "a1mpc_pipeline_submit_ticks_strided_device", "a1mpc_default_preview_config", "a1mpc_horizon_preview_batch", "a1mpc_horizon_preview_batch_device", "a1mpc_solve_batch_ticks_strided", "a1mpc_solve_batch_ticks_strided_device",
            "a1mpc_control_tick_preview_device", "a1mpc_set_timing", "a1mpc_default_tick_params", "a1mpc_control_tick_device", "a1mpc_last_control_tick_ms", "a1mpc_last_stage_ms", "a1mpc_sharded_create", "a1mpc_sharded_solve_batch", "a1mpc_sharded_solve_batch_ticks", "a1mpc_sharded_solve_batch_device", "a1mpc_sharded_solve_batch_ticks_device", "a1mpc_sharded_handle",
            "a1mpc_sharded_last_transfer", "a1mpc_sharded_info", "a1mpc_sharded_destroy", "a1mpc_terrain_batch", "a1mpc_form_qp_batch", "a1mpc_solve_batch_strided", "a1mpc_solve_batch_strided_device", "a1mpc_update_config", "a1mpc_warm_start", "a1mpc_get_warm_start", "a1mpc_get_workspace_z", "a1mpc_get_workspace_scaling", "a1mpc_last_warm_start_mode", "a1mpc_set_profiling", "a1mpc_last_stage_cycles", "a1mpc_last_tick_stage_cycles", "a1mpc_update_plan_batch_device", "a1mpc_swing_legs_batch_device", "a1mpc_contact_terrain_batch_device", "a1mpc_leg_state_batch_device",
            "a1mpc_ekf_update_batch_device", "a1mpc_joint_torques_batch_device", "a1mpc_ekf_update_batch", "a1mpc_reset_ekf_state", "a1mpc_leg_state_batch", "a1mpc_swing_legs_batch", "a1mpc_default_contact_config", "a1mpc_contact_terrain_batch", "a1mpc_reset_contact_state", "a1mpc_default_gait_config", "a1mpc_update_plan_batch", "a1mpc_joint_torques_batch", "a1mpc_set_schedule", "a1mpc_default_config", "a1mpc_default_balance_config", "a1mpc_create", "a1mpc_destroy", "a1mpc_solve_batch",
@@ -167,6 +168,15 @@ def load_library(path=None):
         lib.a1mpc_solve_batch_ticks_strided_device.argtypes = [vp, i32] + [vpp] * 3 + [i32, vpp, i32] + [vpp] * 5 + [vpp]; lib.a1mpc_solve_batch_ticks_strided_device.restype = C.c_int
         lib.a1mpc_control_tick_preview_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(PreviewConfig), C.POINTER(TickBuffers), i32, vp]
         lib.a1mpc_control_tick_preview_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_preview_footholds_device"):   # (the foothold preview; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_horizon_preview_footholds_batch.argtypes = [vp, C.POINTER(PreviewConfig), C.POINTER(GaitConfig), i32, u8p, dp, dp, u8p, dp, dp, dp, dp, u8p, dp]
+        lib.a1mpc_horizon_preview_footholds_batch.restype = C.c_int
+        lib.a1mpc_horizon_preview_footholds_batch_device.argtypes = [vp, C.POINTER(PreviewConfig), C.POINTER(GaitConfig), i32] + [vpp] * 10 + [vpp]
+        lib.a1mpc_horizon_preview_footholds_batch_device.restype = C.c_int
+        lib.a1mpc_control_tick_preview_footholds_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(PreviewConfig), C.POINTER(TickBuffers), i32, vp]
+        lib.a1mpc_control_tick_preview_footholds_device.restype = C.c_int
+        lib.a1mpc_pipeline_submit_ticks_strided_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32p]
+        lib.a1mpc_pipeline_submit_ticks_strided_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_last_tick_stage_cycles"):  # (round 5; an older build bound by hand for an A/B may lack it)
         lib.a1mpc_last_tick_stage_cycles.argtypes = [vp, dp, C.POINTER(C.c_int32)]; lib.a1mpc_last_tick_stage_cycles.restype = C.c_int
     lib.a1mpc_set_schedule.argtypes = [vp, i32]; lib.a1mpc_set_schedule.restype = C.c_int
@@ -334,6 +344,11 @@ class Engine:
         _check(self.lib, self.lib.a1mpc_control_tick_preview_device(self._h, C.byref(params), C.byref(preview), C.byref(buffers), int(n), C.c_void_p(stream) if stream else None),
                "a1mpc_control_tick_preview_device")
 
+    def control_tick_preview_footholds_device(self, params, preview, buffers, n, stream=None):
+        """a1mpc_control_tick_preview_footholds_device: control_tick_preview_device in which a leg that lands inside the horizon stands at buffers.foot_pos_target_abs"""
+        _check(self.lib, self.lib.a1mpc_control_tick_preview_footholds_device(self._h, C.byref(params), C.byref(preview), C.byref(buffers), int(n),
+                                                                              C.c_void_p(stream) if stream else None), "a1mpc_control_tick_preview_footholds_device")
+
     def preview_config(self, **fields):
         """a1mpc_default_preview_config ({1, 0, 1}) with `fields` (contact_schedule, foot_preview, ticks_per_step) overridden"""
         pv = PreviewConfig(); self.lib.a1mpc_default_preview_config(C.byref(pv))
@@ -345,8 +360,9 @@ class Engine:
 
     # ---- the gait-aware horizon: contact schedule (update_plan's counter rule run forward) and per-step feet, the inputs of solve_strided / solve_ticks_strided ----
     def horizon_preview(self, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs=None, R=None, root_lin_vel_d=None, preview=None, gait=None,
-                        want_schedule=True):
-        """dict(contact_sched (n, 4 H) uint8 or None, foot_steps (n, 12 H) or None): a1mpc_horizon_preview_batch.  The feet are produced when preview.foot_preview is 1 or 2."""
+                        want_schedule=True, foot_target_abs=None):
+        """dict(contact_sched (n, 4 H) uint8 or None, foot_steps (n, 12 H) or None): a1mpc_horizon_preview_batch.  The feet are produced when preview.foot_preview is 1 or 2.
+        foot_target_abs (n, 12: update_plan's foot_pos_target_abs) selects a1mpc_horizon_preview_footholds_batch: a leg that lands inside the horizon stands at its target."""
         if gait is None:
             gait = GaitConfig(); self.lib.a1mpc_default_gait_config(C.byref(gait))
         pv = self.preview_config() if preview is None else preview
@@ -357,6 +373,12 @@ class Engine:
         fp = None if foot_pos_abs is None else _f64(foot_pos_abs, (n, 12)); Rw = None if R is None else _f64(R, (n, 9)); vd = None if root_lin_vel_d is None else _f64(root_lin_vel_d, (n, 3))
         sched = np.zeros((n, 4 * h), np.uint8) if want_schedule else None
         feet = np.zeros((n, 12 * h)) if pv.foot_preview != 0 else None
+        if foot_target_abs is not None:
+            tg = _f64(foot_target_abs, (n, 12))
+            rc = self.lib.a1mpc_horizon_preview_footholds_batch(self._h, C.byref(pv), C.byref(gait), n, _u8p(mm), _dp(gc), _dp(spd), _u8p(ct), _dp(fp), _dp(Rw), _dp(vd), _dp(tg),
+                                                                _u8p(sched), _dp(feet))
+            _check(self.lib, rc, "a1mpc_horizon_preview_footholds_batch")
+            return dict(contact_sched=sched, foot_steps=feet)
         rc = self.lib.a1mpc_horizon_preview_batch(self._h, C.byref(pv), C.byref(gait), n, _u8p(mm), _dp(gc), _dp(spd), _u8p(ct), _dp(fp), _dp(Rw), _dp(vd), _u8p(sched), _dp(feet))
         _check(self.lib, rc, "a1mpc_horizon_preview_batch")
         return dict(contact_sched=sched, foot_steps=feet)
@@ -617,6 +639,17 @@ class Pipeline:
         rc = self.lib.a1mpc_pipeline_submit_ticks_device(self._p, int(slot), 1 if fresh else 0, int(n), ptr(d_tick), ptr(d_R), ptr(d_foot), ptr(d_contact), ptr(d_grf), ptr(d_u),
                                                          ptr(d_iters), ptr(d_status), C.c_void_p(int(after_stream)) if after_stream else None, C.byref(k))
         _check(self.lib, rc, "a1mpc_pipeline_submit_ticks_device")
+        return int(k.value)
+
+    def submit_ticks_strided_device(self, n, d_tick, d_R, d_foot, foot_stride, d_contact, contact_stride, d_grf, d_u=None, d_iters=None, d_status=None, d_yaw_A=None,
+                                    slot=-1, fresh=True, after_stream=None):
+        """a1mpc_pipeline_submit_ticks_strided_device: tick records with per-step feet / a contact schedule / an A_c yaw of its own, batches in flight together"""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        k = C.c_int32(-1)
+        rc = self.lib.a1mpc_pipeline_submit_ticks_strided_device(self._p, int(slot), 1 if fresh else 0, int(n), ptr(d_tick), ptr(d_R), ptr(d_foot), int(foot_stride),
+                                                                 ptr(d_contact), int(contact_stride), ptr(d_yaw_A), ptr(d_grf), ptr(d_u), ptr(d_iters), ptr(d_status),
+                                                                 C.c_void_p(int(after_stream)) if after_stream else None, C.byref(k))
+        _check(self.lib, rc, "a1mpc_pipeline_submit_ticks_strided_device")
         return int(k.value)
 
     def submit_strided(self, x0, xref, R, foot, foot_stride, contact, contact_stride, out, yaw_A=None, slot=-1, fresh=True):

@@ -457,6 +457,32 @@ a1mpc_status a1mpc_horizon_preview_batch_device(a1mpc_handle h, const a1mpc_prev
                                                 const uint8_t* d_contacts, const double* d_foot_pos_abs, const double* d_R_world, const double* d_root_lin_vel_d,
                                                 uint8_t* d_contact_sched_out, double* d_foot_steps_out, void* hip_stream);
 /*
+ * The preview with FOOTHOLDS: a leg that the schedule lifts and puts down again inside the horizon stands, from its touchdown on, where update_plan has just planned it
+ * (the Raibert foothold foot_pos_target_abs, S/A1RobotControl.cpp:166-199, the third output of a1mpc_update_plan_batch), not at the place it left.  The QP then knows
+ * where a swing leg lands as well as when.  Not in the reference (which uses the current feet at every step, S/A1RobotControl.cpp:498-514).
+ * For robot i, leg l, steps t = 0 .. H-1, with c_t the contact bit of the schedule the same a1mpc_preview_config produces (c_0 = contacts[]; contact_schedule 0:
+ * contacts[] at every step), s = v * dt rounded once (v, dt as for foot_preview 1 / 2 above) and T = foot_pos_target_abs[i][3l .. 3l+2]:
+ *   f_0 = foot_pos_abs
+ *   f_t = T             if c_t == 1 and c_(t-1) == 0   (a touchdown: the words of T, copied)
+ *   f_t = f_(t-1) - s   otherwise                      (the recurrence of S/test/test_mpc.cpp:112-115, continued from whatever f_(t-1) is)
+ * A second touchdown of the leg inside the horizon is T again; swing steps carry the shifted value (their forces are bound to zero); with contact_schedule 0 there is
+ * no touchdown and the feet are a1mpc_horizon_preview_batch's.  Not predicted: the target of a LATER touchdown is today's (constant velocity and command), and there is
+ * no terrain height at the foothold.  Bit-identical to the plain C++ loop of these lines (no FMA contraction).
+ * Arguments, layouts and validation of a1mpc_horizon_preview_batch(_device), with foot_pos_target_abs n x 12 (3x4 column-major, a1mpc_update_plan_batch's layout) after
+ * root_lin_vel_d.  Refused in addition, with A1MPC_ERR_INVALID_ARGUMENT and a1mpc_last_error naming the argument: foot_steps_out with a null foot_pos_target_abs; with
+ * contact_schedule 1, foot_steps_out with a null movement_mode, gait_counter, gait_counter_speed or contacts even when contact_sched_out is NULL (the footholds read the
+ * schedule).  With foot_steps_out == NULL the call IS a1mpc_horizon_preview_batch(_device).  a1mpc_preview_config is unchanged: foot_preview 3 stays refused.
+ */
+a1mpc_status a1mpc_horizon_preview_footholds_batch(a1mpc_handle h, const a1mpc_preview_config* cfg, const a1mpc_gait_config* gait, int32_t n,
+                                                   const uint8_t* movement_mode, const double* gait_counter, const double* gait_counter_speed,
+                                                   const uint8_t* contacts, const double* foot_pos_abs, const double* R_world, const double* root_lin_vel_d,
+                                                   const double* foot_pos_target_abs, uint8_t* contact_sched_out, double* foot_steps_out);
+a1mpc_status a1mpc_horizon_preview_footholds_batch_device(a1mpc_handle h, const a1mpc_preview_config* cfg, const a1mpc_gait_config* gait, int32_t n,
+                                                          const uint8_t* d_movement_mode, const double* d_gait_counter, const double* d_gait_counter_speed,
+                                                          const uint8_t* d_contacts, const double* d_foot_pos_abs, const double* d_R_world,
+                                                          const double* d_root_lin_vel_d, const double* d_foot_pos_target_abs, uint8_t* d_contact_sched_out,
+                                                          double* d_foot_steps_out, void* hip_stream);
+/*
  * Tick records (a1mpc_solve_batch_ticks: x0 / x_ref built on the device, S/A1RobotControl.cpp:452-488) joined with the strides of a1mpc_solve_batch_strided.
  * (foot_stride, contact_stride, yaw_A) = (0, 0, NULL) IS a1mpc_solve_batch_ticks(_device): same kernels, same bits.  (0, 4, NULL) runs the fast kernels at their speed
  * (contacts only change bounds and equality rows).  Per-step feet and / or a yaw_A run the general kernels, whose set-up builds x0 / x_ref from the record exactly as
@@ -484,6 +510,14 @@ a1mpc_status a1mpc_solve_batch_ticks_strided_device(a1mpc_handle h, int32_t n, c
  */
 a1mpc_status a1mpc_control_tick_preview_device(a1mpc_handle h, const a1mpc_tick_params* params, const a1mpc_preview_config* preview,
                                                const a1mpc_tick_buffers* buffers, int32_t n, void* hip_stream);
+/*
+ * a1mpc_control_tick_preview_device with the foothold rule of a1mpc_horizon_preview_footholds_batch_device fed from buffers->foot_pos_target_abs, which update_plan
+ * (stage 3 of the same tick, S/A1RobotControl.cpp:198) has just written: bit-identical to the chain with that entry in the preview's place.  buffers->foot_pos_target_abs,
+ * an optional output elsewhere, is mandatory here whenever preview->foot_preview != 0 (a null one is refused, A1MPC_ERR_INVALID_ARGUMENT).  With foot_preview 0 the call
+ * IS a1mpc_control_tick_preview_device: same launches, same bits.  torques_fused = 0 with feet on, as there; a1mpc_last_control_tick_ms reports this tick too.
+ */
+a1mpc_status a1mpc_control_tick_preview_footholds_device(a1mpc_handle h, const a1mpc_tick_params* params, const a1mpc_preview_config* preview,
+                                                         const a1mpc_tick_buffers* buffers, int32_t n, void* hip_stream);
 
 /*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
@@ -688,6 +722,14 @@ a1mpc_status a1mpc_pipeline_submit_ticks_device(a1mpc_pipeline p, int32_t slot, 
                                                 const double* d_R_world, const double* d_foot_abs, const uint8_t* d_contact, double* d_grf_body_out,
                                                 double* d_u_full_out, int32_t* d_iters_out, int32_t* d_status_out, void* inputs_ready_stream,
                                                 int32_t* slot_out);
+/* The tick records joined with the strides (arguments of a1mpc_solve_batch_ticks_strided_device: the outputs of the gait-aware horizon as per-step inputs) with batches
+ * in flight together.  Per-step feet always solve on the general kernels, whose first solves are the ones a second batch in flight helps.  Slots, fresh_batch,
+ * inputs_ready_stream and output life times as for a1mpc_pipeline_submit_strided_device; (foot_stride, contact_stride, yaw_A) = (0, 0, NULL) IS
+ * a1mpc_pipeline_submit_ticks_device; a foot_stride other than 0 / 12 or a contact_stride other than 0 / 4 is refused.  Bit-identical to the lone handle's entry. */
+a1mpc_status a1mpc_pipeline_submit_ticks_strided_device(a1mpc_pipeline p, int32_t slot, int32_t fresh_batch, int32_t n, const double* d_tick,
+                                                        const double* d_R_world, const double* d_foot_abs, int32_t foot_stride, const uint8_t* d_contact,
+                                                        int32_t contact_stride, const double* d_yaw_A, double* d_grf_body_out, double* d_u_full_out,
+                                                        int32_t* d_iters_out, int32_t* d_status_out, void* inputs_ready_stream, int32_t* slot_out);
 a1mpc_status a1mpc_pipeline_wait(a1mpc_pipeline p, int32_t slot);
 a1mpc_status a1mpc_pipeline_join(a1mpc_pipeline p, int32_t slot, void* hip_stream);
 /* a1mpc_pipeline_handle: a host-pointer batch still in flight on the slot is waited for and handed to its caller's output arrays first (its results live in
