@@ -52,3 +52,235 @@ def _oracle_update_ticks(oracle, pr, st, scs, carries):
         o = oracle.mpc_solve_update(pr, st, scs["x0"][b], scs["xref"][b], scs["R"][b], scs["foot"][b], scs["contact"][b], carries[b])
         grf[b] = o["grf"]; it[b] = o["info"].iters; stt[b] = o["info"].status
     return grf, it, stt
+
+
+# ---------------------------------------------------------------------------------------------------------------- gait cycles and phase thresholds
+# The reference's gait counters are small multiples of the speed: once per cycle and leg they land exactly on counter_per_swing (120), on 1.5 x counter_per_swing (180) and on
+# counter_per_gait (240, where fmod gives 0), and every branch of the caller-side kernels compares against one of those values.  The builders below give the tests such counters
+# (exactly representable, so every later counter is exact too) and sensor forces that sit on the force thresholds.
+
+PER_GAIT, PER_SWING = 240.0, 120.0                    # counter_per_gait / counter_per_swing, S/A1CtrlStates.h:24-25
+GAIT_RESET = np.array([0.0, 120.0, 120.0, 0.0])       # what update_plan writes while the robot stands (S/A1RobotControl.cpp:150-153)
+DEFAULT_FOOT_POS = np.array([0.17, 0.15, -0.35, 0.17, -0.15, -0.35, -0.17, 0.15, -0.35, -0.17, -0.15, -0.35])
+FORCE_CONTACT = np.array([0.0, 30.0, np.nextafter(30.0, np.inf), 80.0])               # around foot_force_low = 30 (early contact needs ff > 30)
+FORCE_EKF = np.array([-5.0, 0.0, np.nextafter(50.0, 0.0), 50.0, 100.0, 250.0])        # around the EKF's contact estimate (ff / 100 < 0.5 -> 0), both clamps included
+FORCE_TICK = np.unique(np.concatenate([FORCE_CONTACT, FORCE_EKF]))                    # one foot_force array feeds both stages of the control tick
+
+
+def gait_cycle_fleet(n, speeds=(2.0, 1.5, 3.0, 2.0), stagger_ticks=7):
+    """(gait_counter (n, 4), gait_counter_speed (n, 4)): leg l of every robot runs at speeds[l]; robot b starts stagger_ticks * b ticks after the reset pattern.  At any tick
+    some robot of the fleet is at a lift-off (120), the early-contact mark (180), or the wrap (0)."""
+    spd = np.tile(np.asarray(speeds, dtype=np.float64), (n, 1))
+    gc = np.fmod(GAIT_RESET + spd * float(stagger_ticks) * np.arange(n, dtype=np.float64)[:, None], PER_GAIT)
+    return gc, spd
+
+
+def stand_timetable(n, ticks):
+    """(ticks, n) uint8 movement_mode: walk, stand for 1 .. 5 ticks, walk again -- at another tick for every robot.  A robot that has stood restarts from the reset pattern and
+    has lost its stagger, so only the robots of every other block of eight stand; the other blocks walk throughout and keep every phase of the fleet present (a counter's
+    phase repeats every 120 robots, and b and b + 120 lie in blocks of different kinds)."""
+    t = np.arange(ticks)[:, None]; b = np.arange(n)[None, :]
+    start = ticks // 8 + (11 * b) % max(1, ticks // 2)
+    stand = (t >= start) & (t < start + 1 + b % 5) & ((b // 8) % 2 == 0)
+    return np.where(stand, 0, 1).astype(np.uint8)
+
+
+def gait_loop(gc, spd, mm):
+    """update_plan's counter rule as plain numpy (S/A1RobotControl.cpp:150-164): -> (gait_counter, plan_contacts) after one tick with movement_mode mm (n)"""
+    walk = np.asarray(mm).astype(bool)[:, None]
+    g = np.where(walk, np.fmod(gc + spd, PER_GAIT), GAIT_RESET)
+    return g, np.where(walk, g <= PER_SWING, True).astype(np.uint8)
+
+
+def gait_counts(gc0, spd, mm_table):
+    """the counters after each tick of the timetable (ticks, n, 4) and hits = {x: how often a counter of a walking robot is exactly x after its increment}"""
+    gc = gc0.copy(); seq = []
+    for mm in mm_table:
+        gc, _ = gait_loop(gc, spd, mm); seq.append(gc)
+    seq = np.array(seq); walking = np.asarray(mm_table).astype(bool)[:, :, None]
+    return seq, {x: int(((seq == x) & walking).sum()) for x in (PER_SWING, 1.5 * PER_SWING, 0.0)}
+
+
+def assert_thresholds_are_hit(gc0, spd, mm_table):
+    """The input-side assertion of the gait-cycle tests, made before any kernel output is looked at: over the run the counters equal 120, 180 and 0 at least n times each
+    (once per robot on average).  A run shorter than the fastest leg's cycle (80 ticks at speed 3) cannot reach that; there every single tick must hit each of the three marks
+    on some robot, and the count must reach n * ticks / 160 -- what the slowest leg (160 ticks per cycle at speed 1.5) alone contributes to a uniformly staggered fleet."""
+    ticks, n = np.asarray(mm_table).shape
+    seq, hits = gait_counts(gc0, spd, mm_table)
+    print(f"n {n} ticks {ticks}: gait_counter == 120 / 180 / 0 after the increment {hits[120.0]} / {hits[180.0]} / {hits[0.0]} times")
+    if ticks >= 80:
+        assert min(hits.values()) >= n, hits
+    else:
+        walking = np.asarray(mm_table).astype(bool)[:, :, None]
+        for x in hits:
+            assert ((seq == x) & walking).any(axis=(1, 2)).all() and hits[x] >= n * ticks // 160, (x, hits)
+    return seq, hits
+
+
+def threshold_forces(rng, shape, values=FORCE_CONTACT):
+    """foot_force drawn from a few values that sit ON the thresholds of the kernels that read it"""
+    return rng.choice(values, size=shape)
+
+
+def tick_inputs_timetable(scen, rng, n, movement_mode, gait_counter_speed, forces=FORCE_TICK):
+    """tick_inputs with the given movement_mode (one row of stand_timetable) and per-leg speeds, and foot_force on the thresholds"""
+    inp = tick_inputs(scen, rng, n)
+    inp.update(movement_mode=np.ascontiguousarray(movement_mode, dtype=np.uint8), gait_counter_speed=np.ascontiguousarray(gait_counter_speed, dtype=np.float64),
+               foot_force=threshold_forces(rng, (n, 4), forces))
+    return inp
+
+
+def tick_world(n, dev, counters):
+    """the device arrays of one handle's control ticks (state carried from tick to tick, outputs); counters: (4,) or (n, 4)"""
+    import torch
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    init = dict(gait_counter=np.array(np.broadcast_to(np.asarray(counters, dtype=np.float64), (n, 4))), root_pos=np.tile([0.0, 0.0, 0.3], (n, 1)))
+    return dict(state={k: T(init.get(k, np.zeros((n, m)))) for k, m in TICK_STATE.items()},
+                outs={k: torch.zeros((n, m) if m > 1 else (n,), dtype=torch.float64, device=dev) for k, m in TICK_OUT_F64.items()},
+                u8={k: torch.zeros((n, 4), dtype=torch.uint8, device=dev) for k in ("estimated_contacts", "plan_contacts", "contacts")},
+                i32={k: torch.zeros(n, dtype=torch.int32, device=dev) for k in ("iters", "status")})
+
+
+def tick_buffers(E, inp, w):
+    bf = E.TickBuffers()
+    for k in E.TICK_BUFFER_FIELDS:
+        src = inp if k in inp else next(g for g in (w["state"], w["outs"], w["u8"], w["i32"]) if k in g)
+        setattr(bf, k, src[k].data_ptr())
+    return bf
+
+
+def assert_worlds_equal(t, w1, w2):
+    """every output and carried state of two tick worlds, NaN-aware"""
+    for grp in ("state", "outs", "u8", "i32"):
+        for k in w1[grp]:
+            a, b = w1[grp][k].cpu().numpy(), w2[grp][k].cpu().numpy()
+            assert np.array_equal(a, b, equal_nan=True), (t, k, np.abs(a.astype(float) - b.astype(float)).max())
+
+
+class TickChain:
+    """One control tick as the *_device entry points chained by hand on a handle of its own: leg state -> EKF -> plan -> swing legs -> contacts / terrain -> MPC from tick
+    records -> joint torques (the seven entries a1mpc_control_tick_device is documented to equal).  With a preview config the solve is a1mpc_horizon_preview_batch_device
+    (footholds=True: a1mpc_horizon_preview_footholds_batch_device fed the chain's own foot_pos_target_abs) + a1mpc_solve_batch_ticks_strided_device; the schedule and the
+    per-step feet it produced stay readable in .sched_d / .feet_d."""
+
+    def __init__(self, eng, prm, n, stream, preview=None, footholds=False):
+        import ctypes as C
+        import torch
+        self.eng, self.prm, self.n, self.st, self.pv, self.footholds = eng, prm, n, stream, preview, footholds
+        self.sp = C.c_void_p(stream.cuda_stream)
+        self.k = {k: np.array(getattr(prm, k)) for k in ("kp_foot", "kd_foot", "km_foot", "rho_fix", "rho_opt")}
+        h = eng.horizon; dev = torch.device("cuda", 0)
+        self.sched_d = torch.zeros((n, 4 * h), dtype=torch.uint8, device=dev) if preview is not None and preview.contact_schedule else None
+        self.feet_d = torch.zeros((n, 12 * h), dtype=torch.float64, device=dev) if preview is not None and preview.foot_preview else None
+
+    def tick(self, inp, w):
+        import ctypes as C
+        import torch
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        dp_ = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        n, prm, sp, st, pv, k = self.n, self.prm, self.sp, self.st, self.pv, self.k
+        s7, o7, b7, j7, L, H_ = w["state"], w["outs"], w["u8"], w["i32"], self.eng.lib, self.eng._h
+        rcs = [L.a1mpc_leg_state_batch_device(H_, n, ptr(inp["joint_pos"]), ptr(inp["joint_vel"]), ptr(inp["R_world"]), ptr(s7["root_pos"]), ptr(s7["root_lin_vel"]),
+                                              dp_(k["rho_fix"]), dp_(k["rho_opt"]), ptr(o7["foot_pos_rel"]), ptr(o7["j_foot_blocks"]), ptr(o7["foot_vel_rel"]),
+                                              ptr(o7["foot_pos_abs"]), ptr(o7["foot_vel_abs"]), ptr(o7["foot_pos_world"]), ptr(o7["foot_vel_world"]), sp),
+               L.a1mpc_ekf_update_batch_device(H_, n, prm.control_dt, 1, ptr(inp["movement_mode"]), ptr(inp["foot_force"]), ptr(inp["R_world"]), ptr(inp["imu_acc"]),
+                                               ptr(inp["imu_ang_vel"]), ptr(o7["foot_pos_rel"]), ptr(o7["foot_vel_rel"]), ptr(s7["root_pos"]), ptr(s7["root_lin_vel"]),
+                                               ptr(b7["estimated_contacts"]), sp),
+               L.a1mpc_update_plan_batch_device(H_, C.byref(prm.gait), n, ptr(inp["movement_mode"]), ptr(s7["gait_counter"]), ptr(inp["gait_counter_speed"]),
+                                                ptr(s7["root_lin_vel"]), ptr(inp["R_z"]), ptr(inp["R_world"]), ptr(s7["root_pos"]), ptr(inp["root_lin_vel_d"]),
+                                                ptr(b7["plan_contacts"]), ptr(o7["foot_pos_target_rel"]), ptr(o7["foot_pos_target_abs"]), ptr(o7["foot_pos_target_world"]), sp),
+               L.a1mpc_swing_legs_batch_device(H_, n, prm.gait.counter_per_swing, prm.control_dt, ptr(inp["R_z"]), ptr(o7["foot_pos_abs"]), ptr(s7["gait_counter"]),
+                                               ptr(o7["foot_pos_target_rel"]), dp_(k["kp_foot"]), dp_(k["kd_foot"]), ptr(s7["foot_pos_start"]),
+                                               ptr(s7["foot_pos_rel_last_time"]), ptr(s7["foot_pos_target_last_time"]), ptr(o7["foot_pos_cur"]), ptr(o7["foot_forces_kin"]), sp)]
+        with torch.cuda.stream(st):
+            pz = s7["root_pos"][:, 2].contiguous(); pitch = s7["root_euler_d"][:, 1].contiguous()
+        rcs.append(L.a1mpc_contact_terrain_batch_device(H_, C.byref(prm.contact), n, ptr(s7["gait_counter"]), ptr(b7["plan_contacts"]), ptr(inp["foot_force"]),
+                                                        ptr(o7["foot_pos_abs"]), ptr(pz), ptr(pitch), ptr(b7["contacts"]), ptr(o7["foot_pos_recent_contact"]),
+                                                        ptr(o7["terrain_angle"]), sp))
+        with torch.cuda.stream(st):
+            s7["root_euler_d"][:, 1] = pitch
+            tick = torch.cat([inp["root_euler"], s7["root_pos"], inp["root_ang_vel"], s7["root_lin_vel"], s7["root_euler_d"], inp["root_lin_vel_d"], inp["root_ang_vel_d"],
+                              inp["root_pos_d_z"].reshape(n, 1)], 1).contiguous()
+        if pv is None:
+            rcs.append(L.a1mpc_solve_batch_ticks_device(H_, n, ptr(tick), ptr(inp["R_world"]), ptr(o7["foot_pos_abs"]), ptr(b7["contacts"]), ptr(o7["grf"]), None,
+                                                        ptr(j7["iters"]), ptr(j7["status"]), sp))
+        else:
+            sched, feet = self.sched_d, self.feet_d
+            head = (H_, C.byref(pv), C.byref(prm.gait), n, ptr(inp["movement_mode"]), ptr(s7["gait_counter"]), ptr(inp["gait_counter_speed"]), ptr(b7["contacts"]),
+                    ptr(o7["foot_pos_abs"]), ptr(inp["R_world"]), ptr(inp["root_lin_vel_d"]))
+            if self.footholds:
+                rcs.append(L.a1mpc_horizon_preview_footholds_batch_device(*head, ptr(o7["foot_pos_target_abs"]), ptr(sched), ptr(feet), sp))
+            else:
+                rcs.append(L.a1mpc_horizon_preview_batch_device(*head, ptr(sched), ptr(feet), sp))
+            rcs.append(L.a1mpc_solve_batch_ticks_strided_device(H_, n, ptr(tick), ptr(inp["R_world"]), ptr(feet if feet is not None else o7["foot_pos_abs"]),
+                                                                12 if feet is not None else 0, ptr(sched if sched is not None else b7["contacts"]),
+                                                                4 if sched is not None else 0, None, ptr(o7["grf"]), None, ptr(j7["iters"]), ptr(j7["status"]), sp))
+        rcs.append(L.a1mpc_joint_torques_batch_device(H_, n, ptr(inp["mpc_active"]), ptr(b7["contacts"]), ptr(o7["j_foot_blocks"]), ptr(o7["grf"]), ptr(o7["foot_forces_kin"]),
+                                                      dp_(k["km_foot"]), ptr(inp["torques_gravity"]), ptr(s7["joint_torques"]), sp))
+        assert not any(rcs), (rcs, L.a1mpc_last_error())
+
+
+# ---- N2b at its thresholds: the same rows for the GPU entry (tests/test_gpu_gait_cycle.py) and the host-compiled kernel text (tests/test_n2b_host.py) ----
+_UP180, _UP30 = np.nextafter(180.0, np.inf), np.nextafter(30.0, np.inf)
+# per tick (gait_counter, plan_contact, foot_force, the contact the reference computes: S/A1RobotControl.cpp:256-271).  An early contact needs gc > 180 AND ff > 30 and is
+# kept until gc <= 180 clears it, whatever the force does meanwhile.
+CONTACT_SCRIPTS = [
+    # the early-contact flag from tick to tick: set, kept at a low force up to the wrap, cleared in stance, NOT set again at 180 exactly
+    [(182.0, 0, 80.0, 1), (184.0, 0, 5.0, 1), (238.0, 0, 5.0, 1), (0.0, 1, 5.0, 1), (122.0, 0, 5.0, 0), (180.0, 0, 80.0, 0)],
+    # the two comparisons on their own: 180 / the next double, 30 / the next double (the 180 row in between clears the flag)
+    [(180.0, 0, 80.0, 0), (_UP180, 0, 80.0, 1), (180.0, 0, 80.0, 0), (182.0, 0, 30.0, 0), (182.0, 0, _UP30, 1), (182.0, 0, 0.0, 1)],
+]
+Z_STANDING = np.array([0.1, np.nextafter(0.1, 1.0), 0.3])    # root_pos_z > 0.1 is "standing": 0.1 itself is not
+
+
+def contact_threshold_run(step, oracle, n, angle_tol):
+    """The scripts above tiled over n robots x 4 legs (robot b, leg l runs script (b + l) % 2) for six ticks, root_pos_z cycling through Z_STANDING, feet on the plane
+    z = 0.2 x - 0.3.  First the ORACLE is held to the tabulated contacts and to the standing rule, then `step` (gait_counter, plan, foot_force, foot_pos_abs, root_pos_z,
+    pitch -> dict) to the oracle: contacts and filtered positions bit for bit, terrain angle and pitch within angle_tol."""
+    which = (np.arange(n)[:, None] + np.arange(4)[None, :]) % 2
+    z = Z_STANDING[np.arange(n) % 3]
+    xy = np.outer([0.2, 0.2, -0.2, -0.2], [1.0, 0.0]) + np.outer([1, -1, 1, -1], [0.0, 0.13])
+    foot = np.tile(np.c_[xy, 0.2 * xy[:, 0] - 0.3].reshape(12), (n, 1))
+    states = [oracle.contact_state() for _ in range(n)]
+    pitch_k = np.full(n, 0.125); pitch_o = np.full(n, 0.125)
+    seen = set()
+    for t in range(6):
+        row = np.array([[CONTACT_SCRIPTS[s][t] for s in w] for w in which])   # (n, 4, 4)
+        gc, plan, ff, expect = row[:, :, 0], row[:, :, 1].astype(np.uint8), row[:, :, 2], row[:, :, 3].astype(np.uint8)
+        ref = [oracle.contact_terrain_step(states[b], gc[b], plan[b], ff[b], foot[b], z[b], pitch_o[b]) for b in range(n)]
+        ct_o = np.array([r[0] for r in ref]); rec_o = np.array([r[1] for r in ref]); ang_o = np.array([r[2] for r in ref]); pitch_o = np.array([r[3] for r in ref])
+        assert np.array_equal(ct_o, expect), (t, np.argwhere(ct_o != expect)[:4])
+        assert (ang_o[z <= 0.1] == 0.0).all() and (pitch_o[z <= 0.1] == 0.0).all() and (ang_o[z > 0.1] > 0.0).all(), t   # z = 0.1: no angle is filtered, the pitch is +-0
+        seen |= set(expect.ravel().tolist())
+        out = step(gc, plan, ff, foot, z, pitch_k); pitch_k = out["root_euler_d_pitch"]
+        assert np.array_equal(out["contacts"], ct_o), (t, np.argwhere(out["contacts"] != ct_o)[:4])
+        assert np.array_equal(out["foot_pos_recent_contact"], rec_o), t
+        da, dp = np.abs(out["terrain_angle"] - ang_o).max(), np.abs(pitch_k - pitch_o).max()
+        assert da <= angle_tol and dp <= angle_tol, (t, da, dp)
+        assert (out["terrain_angle"][z <= 0.1] == 0.0).all() and (out["terrain_angle"][z > 0.1] > 0.0).all(), t
+    assert seen == {0, 1}
+
+
+def steep_plane_run(step, oracle, angle_tol, n=8, ticks=110):
+    """All feet in contact on the plane z = +-0.75 x - 0.3 (rising for even robots, falling for odd ones): atan(0.75) = 0.6435 rad averaged over the 100-tick window passes
+    the 0.5 clamp at tick 77, and root_euler_d_pitch ends at -0.5 (rising: F_R_diff > 0.05) / +0.5 (falling).  Both signs of the branch and the clamp are asserted to have
+    occurred in the ORACLE's run; `step` is held to the oracle on every tick."""
+    sign = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+    xy = np.outer([0.2, 0.2, -0.2, -0.2], [1.0, 0.0]) + np.outer([1, -1, 1, -1], [0.0, 0.13])
+    foot = np.array([np.c_[xy, s * 0.75 * xy[:, 0] - 0.3].reshape(12) for s in sign])
+    gc = np.zeros((n, 4)); plan = np.ones((n, 4), np.uint8); ff = np.full((n, 4), 80.0); z = np.full(n, 0.3)
+    states = [oracle.contact_state() for _ in range(n)]
+    pitch_k = np.zeros(n); pitch_o = np.zeros(n)
+    first_clamped = None
+    for t in range(ticks):
+        ref = [oracle.contact_terrain_step(states[b], gc[b], plan[b], ff[b], foot[b], z[b], pitch_o[b]) for b in range(n)]
+        ang_o = np.array([r[2] for r in ref]); pitch_o = np.array([r[3] for r in ref])
+        if first_clamped is None and (ang_o == 0.5).all():
+            first_clamped = t
+        out = step(gc, plan, ff, foot, z, pitch_k); pitch_k = out["root_euler_d_pitch"]
+        assert np.array_equal(out["contacts"], np.array([r[0] for r in ref])) and np.array_equal(out["foot_pos_recent_contact"], np.array([r[1] for r in ref])), t
+        da, dp = np.abs(out["terrain_angle"] - ang_o).max(), np.abs(pitch_k - pitch_o).max()
+        assert da <= angle_tol and dp <= angle_tol, (t, da, dp)
+    assert first_clamped == 77, first_clamped
+    assert (pitch_o[sign > 0] == -0.5).all() and (pitch_o[sign < 0] == 0.5).all(), pitch_o
+    assert np.array_equal(pitch_k, pitch_o)   # the clamp value itself is exact on either side

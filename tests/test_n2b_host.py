@@ -37,3 +37,16 @@ def test_n2b_terrain_only_entry_shares_the_terrain_filter(oracle):
         oa = A.tick(gcs, plan, ff, foot, z, pa); pa = oa["root_euler_d_pitch"]
         ob = B.tick(gcs, plan, ff, foot, z, pb, recent_in=oa["foot_pos_recent_contact"]); pb = ob["root_euler_d_pitch"]
         assert np.array_equal(oa["terrain_angle"], ob["terrain_angle"]) and np.array_equal(pa, pb)
+
+
+def test_n2b_kernel_text_at_the_phase_and_force_thresholds(oracle):
+    """The comparisons of the contact logic ON their thresholds, where uniform random counters never land: gait_counter = 180 against the next double, foot_force = 30
+    against the next double, the early-contact flag kept from tick to tick and cleared in stance, root_pos_z = 0.1 (not standing) against the next double, and a plane steep
+    enough that the terrain angle reaches its 0.5 clamp with both signs of the pitch (gpu_common.contact_threshold_run / steep_plane_run: the oracle is held to the
+    tabulated contacts first, then the kernel text to the oracle; the same rows run on the GPU in tests/test_gpu_gait_cycle.py).  Same libm on the host: the angles are exact."""
+    import gpu_common
+    n = 67
+    H = n2b_host.HostN2b(80)
+    gpu_common.contact_threshold_run(H.tick, oracle, n, 0.0)
+    S = n2b_host.HostN2b(8)
+    gpu_common.steep_plane_run(S.tick, oracle, 0.0)
