@@ -26,7 +26,7 @@
 //   * The ADMM state is carried unscaled in the w form (xh, wh0, wh1, rr0, rr1, sigma-term: 6 doubles per horizon
 //     step and lane, + d_t between the sweeps) in VGPRs for the whole solve; all horizon loops over them are fully
 //     unrolled (template H), the Riccati factor loop is not.  While rho is small the iterations also carry
-//     G = c P x + c g through the x-update identity (RowSolver::careful).
+//     G = c P x + c g through the x-update identity (kRhoCareful, RowSolver::advance).
 //   * Drivers: solve_row (fused: set-up + solve, also the latency variant whose four rows share one QP's Ruiz
 //     passes, RowSolver::coop_n), setup_row + admm_rows (split pipeline: persistent rows drain a work queue).
 //
@@ -169,7 +169,7 @@ A1_DEV double dot_bc(const double (&m)[N], double x, double init = 0.0) {
     });
     return a0 + a1;
 }
-// below this rho the dual residual at a checkpoint is dominated by the x-update's backward error unless c P x + c g is carried (RowSolver::careful)
+// below this rho the dual residual at a checkpoint is dominated by the x-update's backward error unless c P x + c g is carried (RowSolver::advance, the CAREFUL variant of admm_iteration)
 constexpr double kRhoCareful = 1e-3;
 constexpr double kSigGeneralPath = 2251799813685248.0;   // 2^51: tag of a pattern signature (Carry<H>::SIG) written by the general path; its hash stays below 2^50
 // gamma_st = alpha_st / beta_st and beta_st = H - max(s,t) never grow with t for fixed s (csrc/a1mpc_tables.hpp; the quotients are compared as integers,
@@ -274,7 +274,7 @@ struct Layout {
     static constexpr int S_SZ = 78;          // packed S_t^{-1}: the 78 entries i >= j, placed by kSinvSlot
     static constexpr int SLOT = K_SZ + S_SZ; // 234 doubles per horizon step
     static constexpr int FAC = 0;
-    static constexpr int GCOL = 12;          // the pad column of K_t's stride-13 rows carries G_t = (c P x + c g)_t, see RowSolver::careful
+    static constexpr int GCOL = 12;          // the pad column of K_t's stride-13 rows carries G_t = (c P x + c g)_t, see kRhoCareful / RowSolver::advance
     static constexpr int BL = H * SLOT;      // B~ (6x12): rows 0-2 = dt*Iw^-1*skew(r), rows 3-5 = dt/m*I
     static constexpr int ZROW = 6;           // a seventh, all-zero row of B~: the row of every lane that owns no wrench state
     static constexpr int CG = BL + 84;       // c*g = D^-1 q_s, [t][12]
@@ -437,7 +437,9 @@ struct RowSolver {
     bool upd;         // warm_start = 2 and a previous tick in the carry: this solve follows the reference's update path
     double epsv[HS];  // set-up, update path: A'[(2 - alpha) rr delta] of my lane (the first iteration's correction of c g)
     int coop_id = 0, coop_n = 1;  // set-up only: row coop_id of coop_n rows of the wave that work on the SAME QP (batch-1 latency path), sharing its LDS image
-    bool careful;  // rho is small: c P x + c g is carried through the x-update identity (G in LDS) instead of re-evaluated at the checkpoints
+    // `careful` (a predicate of rho and iter, not a member: the flag cost the hot loops a register they do not have): while rho <= kRhoCareful, c P x + c g is carried through
+    // the x-update identity (G in LDS) instead of re-evaluated at the checkpoints.  G is seeded by the checkpoint at which a rho update lands there or, for a solve that starts
+    // there, by a checkpoint of its own after iteration 1 (advance)
     // bookkeeping
     int iter, nfact;
     int32_t status;
@@ -476,7 +478,7 @@ struct RowSolver {
         r2a = act ? P.r2[ci] : 0.0;      // force-lane weight 2 r_a
         r0 = comp == 0 ? 0 : (comp == 1 ? 2 : 4); r1 = comp == 0 ? 1 : 3;
         iter = 0; nfact = 0; status = A1MPC_UNSOLVED; fac_ok = true; need_factor = true; done = false;
-        warm = false; first_special = false; eqmask = 0; careful = false; upd = false;
+        warm = false; first_special = false; eqmask = 0; upd = false;
     }
 
     // the one lane that speaks for this QP (scalar outputs, the work queue)
@@ -1260,7 +1262,7 @@ struct RowSolver {
                 if (ln == 0) cw[CR::C] = csc;
             }
         }
-        iter = 0; nfact = 0; status = A1MPC_UNSOLVED; fac_ok = true; need_factor = true; done = false; careful = false;
+        iter = 0; nfact = 0; status = A1MPC_UNSOLVED; fac_ok = true; need_factor = true; done = false;
     }
 
     // Queue-order heuristic for a batch without history (scheduling only, no result depends on it): ADMM needs more iterations the more
@@ -1404,7 +1406,7 @@ struct RowSolver {
                 sync();
             }
         }
-        iter = 0; nfact = 0; status = A1MPC_UNSOLVED; fac_ok = true; need_factor = true; done = false; careful = false;
+        iter = 0; nfact = 0; status = A1MPC_UNSOLVED; fac_ok = true; need_factor = true; done = false;
         pfX = pfT = pfU = 0;
 #ifdef A1X_CLK
         clkB = clkF = clkT = clkU = clkX = 0;
@@ -2017,7 +2019,7 @@ struct RowSolver {
             // of the Riccati solves -- the value carried through the x-update identity by the iterations (G, in the unused K_0 slot)
             double* G = lds + L::FAC + t * L::SLOT + ci * L::KSTR + L::GCOL;
             double pq_u = px_u + cgt;
-            if (careful) pq_u = act ? *G : 0.0;
+            if (rho <= kRhoCareful && iter > 1) pq_u = act ? *G : 0.0;   // careful (rho is the one the iterations up to here ran at; iter == 1: the seeding checkpoint)
             else if (act) *G = pq_u;
             const double rd_u = pq_u + aty_u;        // = D^-1 (P_s x_s + q_s + A_s' y_s)
             const double D2 = one_c / dI2[k];        // D^2
@@ -2077,6 +2079,9 @@ struct RowSolver {
             int next = P.max_iter;
             if (P.check_every > 0) next = imin(next, (iter / P.check_every + 1) * P.check_every);
             if (P.adaptive_rho && P.adaptive_rho_every > 0) next = imin(next, (iter / P.adaptive_rho_every + 1) * P.adaptive_rho_every);
+            // a solve that STARTS at a small rho (a warm-started tick whose predecessor adapted rho down, or a configured rho that small) has no rho update whose checkpoint
+            // seeds G: its first segment ends after iteration 1, update_info() evaluates G there once (iter > 1 fails) and the iterations carry it from iteration 2 on
+            if (iter == 0 && rho <= kRhoCareful) next = imin(next, 1);
             if (iter == 0 && first_special) {
                 admm_iteration<true>(); iter = 1;
                 if constexpr (UPD && H > 1 && !SETUP_ONLY && MODE == kModeMpc) restore_cg();  // (unconditional in the UPD instantiations: a flag would have to live across the ADMM loop)
@@ -2094,7 +2099,7 @@ struct RowSolver {
 #endif
             [[maybe_unused]] long long pf1_ = 0;
             if constexpr (CLK) pf1_ = row_clock();
-            if (row_wave_any(careful)) {
+            if (row_wave_any(rho <= kRhoCareful && iter > 0)) {   // careful
                 for (int k = iter; k < next; ++k) admm_iteration<false, true>();
             } else {
                 for (int k = iter; k < next; ++k) admm_iteration<false, false>();
@@ -2137,7 +2142,6 @@ struct RowSolver {
                         });
                         rho = rn;
                         need_factor = true;
-                        careful = rho <= kRhoCareful;  // G holds this checkpoint's evaluation (written by update_info above) or the carried value
                     }
                 }
                 if (last) {

@@ -223,6 +223,13 @@ def test_emulated_twin_rows_warm_start_first_iteration_and_small_rho(oracle, sce
     over = dict(rho0=1e-5, adaptive_rho=0, max_iter=60)   # rho <= kRhoCareful from the start
     a = emu.solve(sc, 3, **over); b = emu.solve(sc, 3, twin=True, **over)
     assert np.array_equal(a["u"], b["u"]) and (a["iters"] == b["iters"]).all()
+    # ... and a solve that STARTS there is held to the oracle: G is seeded by a checkpoint of its own after iteration 1 (RowSolver::advance), with the rho estimate taken
+    # from the carried value (adaptive rho on) and without it
+    for kw, okw in ((over, dict(rho=1e-5, adaptive_rho=0, max_iter=60)), (dict(rho0=1e-4), dict(rho=1e-4))):
+        ref = oracle_batch(oracle, sc, 3, settings=oracle.default_settings(**okw))
+        for out in (emu.solve(sc, 3, **kw), emu.solve(sc, 3, twin=True, **kw)):
+            assert (out["nfact"] == ref["nfact"]).all()
+            compare(out, ref, tol=1e-8, min_same=1.0)
 
 
 def test_emulated_twin_rows_non_finite_input(oracle, scen):

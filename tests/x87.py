@@ -74,11 +74,15 @@ def mpc_solve_update(pr, st, x0, xref, Rw, foot, contact, carry):
     return dict(grf=grf.astype(np.float64), u=u.astype(np.float64), iters=int(info.iters), status=int(info.status))
 
 
-def mpc_solve(pr, st, x0, xref, Rw, foot, contact):
-    """one cold solve (orc_mpc_solve in extended precision): dict(grf, iters, status)"""
-    grf = np.zeros(12, np.longdouble); info = InfoX()
+def mpc_solve(pr, st, x0, xref, Rw, foot, contact, foot_stride=0, contact_stride=0, warm_x=None, warm_y=None, warm_rho=None):
+    """one solve (orc_mpc_solve in extended precision): dict(grf, u, iters, status).  foot_stride / contact_stride: per-step feet / a contact schedule, as in
+    oracle.mpc_solve; warm_x / warm_y / warm_rho (doubles, not modified): the state a warm_start = 1 solve starts from (st.warm_start must be 1), cold without them."""
+    grf = np.zeros(12, np.longdouble); u = np.zeros(12 * pr.horizon, np.longdouble); info = InfoX()
     ct = np.ascontiguousarray(contact, dtype=np.uint8)
     X0, XR, RW, FT = _ld(x0), _ld(xref), _ld(Rw), _ld(foot)
-    lib().orc_mpc_solve(C.byref(pr), C.byref(st), _ldp(X0), _ldp(XR), _ldp(RW), _ldp(FT), C.c_int(0), ct.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int(0), _ldp(grf),
-                        None, None, None, None, C.byref(info))
-    return dict(grf=grf.astype(np.float64), iters=int(info.iters), status=int(info.status))
+    wx = None if warm_x is None else _ld(warm_x); wy = None if warm_y is None else _ld(warm_y)
+    rho = LD(0.0 if warm_rho is None else float(warm_rho))
+    lib().orc_mpc_solve(C.byref(pr), C.byref(st), _ldp(X0), _ldp(XR), _ldp(RW), _ldp(FT), C.c_int(int(foot_stride)), ct.ctypes.data_as(C.POINTER(C.c_uint8)),
+                        C.c_int(int(contact_stride)), _ldp(grf), _ldp(u), None if wx is None else _ldp(wx), None if wy is None else _ldp(wy),
+                        C.byref(rho), C.byref(info))
+    return dict(grf=grf.astype(np.float64), u=u.astype(np.float64), iters=int(info.iters), status=int(info.status))
