@@ -368,6 +368,179 @@ __global__ __launch_bounds__(256) void a1mpc_horizon_preview_footholds_kernel(co
     if (live) preview_feet<true>(a, b, leg, H, m);
 }
 
+// ---- predicted horizon states and the cost of a force plan (a1mpc_horizon_states_batch): x_(t+1) = A_d x_t + B_d,t u_t rolled out from x0, i.e. A_qp x0 + B_qp u of the
+// reference's public members (S/ConvexMpc.h, S/ConvexMpc.cpp:181-202) without forming either, and the two sums 1/2 e'Qe, 1/2 u'Ru.  Memory-bound: 25H + 34 doubles in,
+// 13H + 2 out per QP.
+//   lanes     one wavefront = one workgroup = 16 consecutive QPs, lane = 4 * (QP of the wave) + l.  Lane l holds leg l's foot and force (the cross product needs no
+//             exchange) and owns state triple l: 0 rpy, 1 pos, 2 omega, 3 v.  The pair sums over legs {0,1} / {2,3} are one exchange with lane ^ 1; the second step is
+//             folded into the exchange with lane ^ 2 that also hands the old omega, v to lanes 0, 1: lanes 0 / 1 send their pair's torque / force, lanes 2 / 3 their old
+//             state -- every x_t is read before any x_(t+1) is written.  Sum order: (leg 0 + leg 1) + (leg 2 + leg 3).  Plain wave shuffles (64-bit DPP has row_newbcast only).
+//   memory    the wave's QPs own ONE contiguous run of u_full, x_ref, the per-step feet and x_pred.  The run is visited kHsChunk steps at a time: the chunk of every array
+//             goes through wave-private LDS, 64 consecutive doubles of the chunk per instruction, so that global memory sees pieces of 12 (13) * kHsChunk consecutive
+//             doubles per QP (384 / 416 B) instead of one 24-byte triple per lane at a stride of 96H bytes.  x_pred takes x_ref's place in LDS (a lane reads its three
+//             reference words, then writes its three state words over them).  Rows of 52 doubles: the 8 QPs of a half wave start 40 banks apart (mod 64), the reads of a
+//             component are conflict-free.  3 * 16 * 52 doubles = 19 968 B per wave: eight waves per CU.
+//   bits      contraction off, fma() where a product feeds a sum: the results do not depend on where the compiler places the code, nor on the number of QPs in the call.
+//   dead lanes (QPs >= n of the last wave) read the wave's first QP, take part in every shuffle and store nothing, neither to LDS nor to memory.
+struct HorizonStatesArgs {
+    int32_t n, H, foot_stride;
+    double dt, mass, inertia[9], q[12], r[12];
+    const double *x0, *tick, *xref, *R, *foot, *yaw_A, *u;   // x0 (n x 13) or tick (n x 22); xref, yaw_A, u may be null
+    double *x_pred, *cost;                                   // n x 13H, n x 2; either may be null
+};
+constexpr int kHsChunk = 4, kHsRow = 52, kHsBuf = 16 * kHsRow;
+static_assert(kHsRow >= 13 * kHsChunk && (2 * kHsRow) % 64 == 40, "a chunk of x_ref fits a row; rows start 40 banks apart");
+// (QP of the wave, offset in its piece) of element e of a chunk whose pieces are cw doubles: e / cw without an integer division (e < 832, cw >= 12: the quotient is
+// never closer than 0.009 to an integer, the float product is off by < 1e-5)
+__device__ __forceinline__ int hs_row(int e, float inv_cw) { return static_cast<int>((static_cast<float>(e) + 0.5f) * inv_cw); }
+// the chunk [t0, t0 + c) of the wave's run of a [QP][H][W] array -> LDS rows (or back): 64 consecutive doubles of the chunk per instruction, all loads issued before the
+// first LDS write.  Only the `live` QPs of the wave are touched: every address lies inside the n x H x W array
+template <int W>
+__device__ __forceinline__ void hs_load(double* buf, const double* g, int64_t first, int live, int H, int t0, int c, int lane) {
+    constexpr int kMax = (16 * kHsChunk * W + 63) / 64;
+    const int cw = c * W, cnt = live * cw;
+    const float inv = 1.0f / static_cast<float>(cw);
+    const double* base = g + (first * H + t0) * W;
+    double v[kMax];
+#pragma unroll
+    for (int m = 0; m < kMax; ++m) {
+        const int e = lane + 64 * m, q = hs_row(e, inv);
+        v[m] = base[e < cnt ? static_cast<int64_t>(q) * H * W + (e - q * cw) : 0];   // (past the chunk: the chunk's first word again, no branch around the load)
+    }
+#pragma unroll
+    for (int m = 0; m < kMax; ++m) {
+        const int e = lane + 64 * m, q = hs_row(e, inv);
+        if (e < cnt) buf[q * kHsRow + (e - q * cw)] = v[m];
+    }
+}
+template <int W>
+__device__ __forceinline__ void hs_store(const double* buf, double* g, int64_t first, int live, int H, int t0, int c, int lane) {
+    constexpr int kMax = (16 * kHsChunk * W + 63) / 64;
+    const int cw = c * W, cnt = live * cw;
+    const float inv = 1.0f / static_cast<float>(cw);
+    double* base = g + (first * H + t0) * W;
+#pragma unroll
+    for (int m = 0; m < kMax; ++m) {
+        const int e = lane + 64 * m, q = hs_row(e, inv);
+        if (e < cnt) base[static_cast<int64_t>(q) * H * W + (e - q * cw)] = buf[q * kHsRow + (e - q * cw)];
+    }
+}
+__device__ __forceinline__ double hs_pick(int l, double a0, double a1, double a2, double a3) { return l == 0 ? a0 : (l == 1 ? a1 : (l == 2 ? a2 : a3)); }
+__global__ __launch_bounds__(64) void a1mpc_horizon_states_kernel(const HorizonStatesArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double lds[3 * kHsBuf];
+    double* const U = lds; double* const F = lds + kHsBuf; double* const X = lds + 2 * kHsBuf;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, H = a.H;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int row = (alive ? qw : 0) * kHsRow;
+    const int64_t b = first + (alive ? qw : 0);
+    // once per QP: the state triple, yaw, Iw^-1, dt / m (the arithmetic of a1mpc_form_kernel)
+    const double* xs = a.tick ? a.tick + b * 22 : a.x0 + b * 13;
+    double x[3] = {xs[3 * l], xs[3 * l + 1], xs[3 * l + 2]};
+    const double grav = a.tick ? -9.8 : xs[12];
+    const double yaw = a.yaw_A ? a.yaw_A[b] : xs[2];
+    const double dt = a.dt, cy = cos(yaw), sy = sin(yaw), bv = dt / a.mass;
+    const double* R = a.R + b * 9;
+    double Ii[9];
+    {   // I_world = R I_b R', inverse by cofactors (S/ConvexMpc.cpp:136-141)
+        double Rm[9], t9[9], Iw[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Rm[i] = R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) t9[i * 3 + j] = fma(Rm[i * 3 + 2], a.inertia[6 + j], fma(Rm[i * 3 + 1], a.inertia[3 + j], Rm[i * 3] * a.inertia[j]));
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Iw[i * 3 + j] = fma(t9[i * 3 + 2], Rm[j * 3 + 2], fma(t9[i * 3 + 1], Rm[j * 3 + 1], t9[i * 3] * Rm[j * 3]));
+        const double c00 = fma(Iw[4], Iw[8], -(Iw[5] * Iw[7])), c01 = fma(Iw[5], Iw[6], -(Iw[3] * Iw[8])), c02 = fma(Iw[3], Iw[7], -(Iw[4] * Iw[6]));
+        const double id = 1.0 / fma(Iw[2], c02, fma(Iw[1], c01, Iw[0] * c00));
+        Ii[0] = c00 * id; Ii[1] = fma(Iw[2], Iw[7], -(Iw[1] * Iw[8])) * id; Ii[2] = fma(Iw[1], Iw[5], -(Iw[2] * Iw[4])) * id;
+        Ii[3] = c01 * id; Ii[4] = fma(Iw[0], Iw[8], -(Iw[2] * Iw[6])) * id; Ii[5] = fma(Iw[2], Iw[3], -(Iw[0] * Iw[5])) * id;
+        Ii[6] = c02 * id; Ii[7] = fma(Iw[1], Iw[6], -(Iw[0] * Iw[7])) * id; Ii[8] = fma(Iw[0], Iw[4], -(Iw[1] * Iw[3])) * id;
+    }
+    // the lane's 3 x 3 block of [A_d - I | B_d] and what it multiplies: rpy <- (dt T) omega, pos <- (dt I) v, omega <- (dt Iw^-1) sum r x f, v <- (dt / m I) sum f  (+ dt g)
+    double M[9];
+    {
+        const double dc = cy * dt, ds = sy * dt;   // A_d = I + A_c dt (S/ConvexMpc.cpp:150)
+        const double dI = l == 1 ? dt : bv;
+        M[0] = hs_pick(l, dc, dI, Ii[0] * dt, dI);  M[1] = hs_pick(l, ds, 0.0, Ii[1] * dt, 0.0); M[2] = hs_pick(l, 0.0, 0.0, Ii[2] * dt, 0.0);
+        M[3] = hs_pick(l, -ds, 0.0, Ii[3] * dt, 0.0); M[4] = hs_pick(l, dc, dI, Ii[4] * dt, dI); M[5] = hs_pick(l, 0.0, 0.0, Ii[5] * dt, 0.0);
+        M[6] = hs_pick(l, 0.0, 0.0, Ii[6] * dt, 0.0); M[7] = hs_pick(l, 0.0, 0.0, Ii[7] * dt, 0.0); M[8] = hs_pick(l, dt, dI, Ii[8] * dt, dI);
+    }
+    const double gz = l == 3 ? dt * grav : 0.0;   // A_d(11, 12) = dt (S/ConvexMpc.cpp:129)
+    const double qk[3] = {hs_pick(l, a.q[0], a.q[3], a.q[6], a.q[9]), hs_pick(l, a.q[1], a.q[4], a.q[7], a.q[10]), hs_pick(l, a.q[2], a.q[5], a.q[8], a.q[11])};
+    const double rk[3] = {hs_pick(l, a.r[0], a.r[3], a.r[6], a.r[9]), hs_pick(l, a.r[1], a.r[4], a.r[7], a.r[10]), hs_pick(l, a.r[2], a.r[5], a.r[8], a.r[11])};
+    const bool want_cost = a.cost != nullptr;
+    // tick record: x_ref_t = base + (slope dt)(t + 1), the set-up's expressions (RowSolver::setup; S/A1RobotControl.cpp:470-488)
+    double xb[3] = {0.0, 0.0, 0.0}, xsl[3] = {0.0, 0.0, 0.0};
+    if (a.tick && want_cost) {
+        const double* k = xs;
+        const double vwx = R[0] * k[15] + R[1] * k[16] + R[2] * k[17], vwy = R[3] * k[15] + R[4] * k[16] + R[5] * k[17];
+        xb[0] = hs_pick(l, k[12], k[3], k[18], vwx); xb[1] = hs_pick(l, k[13], k[4], k[19], vwy); xb[2] = hs_pick(l, k[2], k[21], k[20], 0.0);
+        xsl[0] = l == 1 ? vwx * dt : 0.0; xsl[1] = l == 1 ? vwy * dt : 0.0; xsl[2] = l == 0 ? k[20] * dt : 0.0;
+    }
+    double r0[3] = {0.0, 0.0, 0.0};
+    if (a.foot_stride == 0) { const double* fp = a.foot + b * 12 + 3 * l; r0[0] = fp[0]; r0[1] = fp[1]; r0[2] = fp[2]; }
+    double cx = 0.0, cu = 0.0;
+    for (int t0 = 0; t0 < H; t0 += kHsChunk) {
+        const int c = H - t0 < kHsChunk ? H - t0 : kHsChunk;
+        if (a.u) hs_load<12>(U, a.u, first, live, H, t0, c, lane);
+        if (a.foot_stride) hs_load<12>(F, a.foot, first, live, H, t0, c, lane);
+        if (a.xref && want_cost) hs_load<13>(X, a.xref, first, live, H, t0, c, lane);
+        WaveStage::sync();
+        for (int tt = 0; tt < c; ++tt) {
+            double f[3] = {0.0, 0.0, 0.0}, r[3] = {r0[0], r0[1], r0[2]};
+            if (a.u) { const double* p = U + row + tt * 12 + 3 * l; f[0] = p[0]; f[1] = p[1]; f[2] = p[2]; }
+            if (a.foot_stride) { const double* p = F + row + tt * 12 + 3 * l; r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; }
+            // this leg's r x f and f, summed with the pair's other leg; lanes 0 / 1 then send the pair's torque / force, lanes 2 / 3 their old state
+            double snd[3], w[3];
+            {
+                const double tq[3] = {fma(r[1], f[2], -(r[2] * f[1])), fma(r[2], f[0], -(r[0] * f[2])), fma(r[0], f[1], -(r[1] * f[0]))};
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double pt = tq[k] + __shfl_xor(tq[k], 1, 64), pf = f[k] + __shfl_xor(f[k], 1, 64);
+                    snd[k] = (l & 1) ? pf : pt;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double got = __shfl_xor(l >= 2 ? x[k] : snd[k], 2, 64);
+                w[k] = l >= 2 ? got + snd[k] : got;   // lanes 2 / 3: (leg 0 + leg 1) + (leg 2 + leg 3)
+            }
+            double* xo = X + row + tt * 13 + 3 * l;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                double xn = fma(M[3 * k + 2], w[2], fma(M[3 * k + 1], w[1], fma(M[3 * k], w[0], x[k])));
+                if (k == 2) xn = xn + gz;
+                if (want_cost) {
+                    const double xr = a.tick ? xb[k] + xsl[k] * static_cast<double>(t0 + tt + 1) : xo[k];
+                    const double e = xn - xr;
+                    cx = fma(qk[k] * e, e, cx);
+                    cu = fma(rk[k] * f[k], f[k], cu);
+                }
+                x[k] = xn;
+            }
+            if (alive) {
+                xo[0] = x[0]; xo[1] = x[1]; xo[2] = x[2];
+                if (l == 0) xo[12] = grav;
+            }
+        }
+        WaveStage::sync();
+        if (a.x_pred) hs_store<13>(X, a.x_pred, first, live, H, t0, c, lane);
+        WaveStage::sync();
+    }
+    if (want_cost) {
+        cx = cx + __shfl_xor(cx, 1, 64); cx = cx + __shfl_xor(cx, 2, 64);
+        cu = cu + __shfl_xor(cu, 1, 64); cu = cu + __shfl_xor(cu, 2, 64);
+        if (alive && l == 0) { a.cost[b * 2] = cx; a.cost[b * 2 + 1] = cu; }
+    }
+}
+
 thread_local std::string g_last_error;
 std::mutex g_cache_mu;
 thread_local bool g_clk_ran = false;
@@ -627,6 +800,7 @@ struct a1mpc_handle_s {
     double* d_tickrec = nullptr;    // a1mpc_control_tick_device: n x 22 tick records + 3 doubles (km_foot), allocated on first use
     uint32_t* d_pv_sched = nullptr; // a1mpc_control_tick_preview_device: n x H words, the horizon's contact schedule (allocated on first use)
     double* d_pv_foot = nullptr;    // ... and n x 12H per-step feet (allocated on first use)
+    double *d_hs_u = nullptr, *d_hs_x = nullptr;   // a1mpc_horizon_states_batch (host pointers): n x 12H forces in, n x 13H predicted states out (allocated on first use)
     int32_t ekf_ready_n = 0;        // robots 0 .. ekf_ready_n - 1 have had their filter initialised (the init kernel is not launched for them again)
     // staging of the host-pointer entries of the caller-side stages, allocated on first use (ensure_aux; handed out by Staging)
     double *d_aux_in = nullptr, *d_aux_out = nullptr;
@@ -1753,7 +1927,7 @@ void a1mpc_destroy(a1mpc_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_tab, h->d_tab1, h->d_x0, h->d_xref, h->d_R, h->d_foot, h->d_aux, h->d_Rz, h->d_contact, h->d_grf,
-                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot};
+                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -2379,6 +2553,87 @@ a1mpc_status a1mpc_horizon_preview_footholds_batch(a1mpc_handle h, const a1mpc_p
                                                    double* foot_steps_out) {
     return preview_host_impl(h, pv, gait, n, movement_mode, gait_counter, gait_counter_speed, contacts, foot_pos_abs, R_world, root_lin_vel_d, true, foot_pos_target_abs,
                              sched_out, foot_steps_out);
+}
+
+// ---- predicted horizon states and cost of a force plan: a1mpc_horizon_states_kernel behind the C ABI
+// what the four entries refuse, or null (all before the first HIP call).  `state` is x0 or, for the tick entries, the tick record
+static const char* invalid_horizon_states(a1mpc_handle h, int32_t n, bool ticks, const double* state, const double* x_ref, const double* R_world, const double* foot_abs,
+                                          int32_t foot_stride, const double* x_pred_out, const double* cost_out) {
+    if (!h) return "null handle";
+    if (n < 0) return "negative n";
+    if (n > h->max_batch) return "n > max_batch given to a1mpc_create";
+    if (foot_stride != 0 && foot_stride != 12) return "foot_stride must be 0 or 12";
+    if (!x_pred_out && !cost_out) return "x_pred_out and cost_out are both null";
+    if (!ticks && cost_out && !x_ref) return "cost_out needs x_ref (null)";
+    if (!state) return ticks ? "null tick" : "null x0";
+    if (!R_world) return "null R_world";
+    if (!foot_abs) return "null foot_abs";
+    if (h->cfg.horizon < 2) return "the predicted horizon states need horizon >= 2 (a1mpc_config.horizon)";
+    return nullptr;
+}
+// the launch alone: device pointers, validated by the caller, which also orders and marks the stream.  One wavefront per workgroup, 16 QPs each
+static void launch_horizon_states(a1mpc_handle h, int32_t n, bool ticks, const double* state, const double* x_ref, const double* R_world, const double* foot_abs,
+                                  int32_t foot_stride, const double* yaw_A, const double* u_full, double* x_pred_out, double* cost_out, hipStream_t s) {
+    HorizonStatesArgs a;
+    const a1mpc_config& c = h->cfg;
+    a.n = n; a.H = c.horizon; a.foot_stride = foot_stride; a.dt = c.dt; a.mass = c.mass;
+    for (int i = 0; i < 9; ++i) a.inertia[i] = c.inertia_body[i];
+    for (int i = 0; i < 12; ++i) { a.q[i] = c.q[i]; a.r[i] = c.r[i]; }
+    a.x0 = ticks ? nullptr : state; a.tick = ticks ? state : nullptr; a.xref = ticks ? nullptr : x_ref;
+    a.R = R_world; a.foot = foot_abs; a.yaw_A = yaw_A; a.u = u_full; a.x_pred = x_pred_out; a.cost = cost_out;
+    hipLaunchKernelGGL(a1mpc_horizon_states_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, a);
+}
+static a1mpc_status horizon_states_device_impl(a1mpc_handle h, int32_t n, bool ticks, const double* d_state, const double* d_x_ref, const double* d_R_world,
+                                               const double* d_foot_abs, int32_t foot_stride, const double* d_yaw_A, const double* d_u_full, double* d_x_pred_out,
+                                               double* d_cost_out, void* hip_stream) {
+    if (const char* bad = invalid_horizon_states(h, n, ticks, d_state, d_x_ref, d_R_world, d_foot_abs, foot_stride, d_x_pred_out, d_cost_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_horizon_states(h, n, ticks, d_state, d_x_ref, d_R_world, d_foot_abs, foot_stride, d_yaw_A, d_u_full, d_x_pred_out, d_cost_out, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_horizon_states_batch_device(a1mpc_handle h, int32_t n, const double* d_x0, const double* d_x_ref, const double* d_R_world, const double* d_foot_abs,
+                                               int32_t foot_stride, const double* d_yaw_A, const double* d_u_full, double* d_x_pred_out, double* d_cost_out,
+                                               void* hip_stream) {
+    return horizon_states_device_impl(h, n, false, d_x0, d_x_ref, d_R_world, d_foot_abs, foot_stride, d_yaw_A, d_u_full, d_x_pred_out, d_cost_out, hip_stream);
+}
+a1mpc_status a1mpc_horizon_states_ticks_batch_device(a1mpc_handle h, int32_t n, const double* d_tick, const double* d_R_world, const double* d_foot_abs,
+                                                     int32_t foot_stride, const double* d_yaw_A, const double* d_u_full, double* d_x_pred_out, double* d_cost_out,
+                                                     void* hip_stream) {
+    return horizon_states_device_impl(h, n, true, d_tick, nullptr, d_R_world, d_foot_abs, foot_stride, d_yaw_A, d_u_full, d_x_pred_out, d_cost_out, hip_stream);
+}
+// the host-pointer entries: the per-QP arrays go through Staging, the per-step ones (13H / 12H doubles per QP, more than its slices hold) through the handle's
+// per-step buffers -- d_xref and d_foot_steps, which the solve entries' host paths fill anew at every call, and two of this stage's own
+static a1mpc_status horizon_states_host_impl(a1mpc_handle h, int32_t n, bool ticks, const double* state, const double* x_ref, const double* R_world, const double* foot_abs,
+                                             int32_t foot_stride, const double* yaw_A, const double* u_full, double* x_pred_out, double* cost_out) {
+    if (const char* bad = invalid_horizon_states(h, n, ticks, state, x_ref, R_world, foot_abs, foot_stride, x_pred_out, cost_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const size_t H = h->cfg.horizon, N = static_cast<size_t>(n), cap = static_cast<size_t>(h->max_batch);
+    if (foot_stride)
+        if (a1mpc_status st = ensure_step_staging(h); st != A1MPC_OK) return st;
+    if (u_full && !h->d_hs_u) A1_HIP(hipMalloc(&h->d_hs_u, cap * 12 * H * sizeof(double)));
+    if (x_pred_out && !h->d_hs_x) A1_HIP(hipMalloc(&h->d_hs_x, cap * 13 * H * sizeof(double)));
+    const double *d_state = sg.in(state, ticks ? 22 : 13), *d_R = sg.in(R_world, 9), *d_yaw = yaw_A ? sg.in(yaw_A, 1) : nullptr;
+    const double* d_foot = foot_stride ? h->d_foot_steps : sg.in(foot_abs, 12);
+    const bool with_ref = !ticks && x_ref && cost_out;   // (x_ref is read by the cost alone)
+    if (with_ref) sg.hip(hipMemcpyAsync(h->d_xref, x_ref, N * 13 * H * sizeof(double), hipMemcpyHostToDevice, s), "hipMemcpyAsync (x_ref)");
+    if (foot_stride) sg.hip(hipMemcpyAsync(h->d_foot_steps, foot_abs, N * 12 * H * sizeof(double), hipMemcpyHostToDevice, s), "hipMemcpyAsync (per-step feet)");
+    if (u_full) sg.hip(hipMemcpyAsync(h->d_hs_u, u_full, N * 12 * H * sizeof(double), hipMemcpyHostToDevice, s), "hipMemcpyAsync (u_full)");
+    double* d_cost = sg.out(cost_out, 2);
+    sg.back(x_pred_out, h->d_hs_x, 13 * H);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_horizon_states(h, n, ticks, d_state, with_ref ? h->d_xref : nullptr, d_R, d_foot, foot_stride, d_yaw, u_full ? h->d_hs_u : nullptr,
+                                          x_pred_out ? h->d_hs_x : nullptr, d_cost, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_horizon_states_batch(a1mpc_handle h, int32_t n, const double* x0, const double* x_ref, const double* R_world, const double* foot_abs, int32_t foot_stride,
+                                        const double* yaw_A, const double* u_full, double* x_pred_out, double* cost_out) {
+    return horizon_states_host_impl(h, n, false, x0, x_ref, R_world, foot_abs, foot_stride, yaw_A, u_full, x_pred_out, cost_out);
+}
+a1mpc_status a1mpc_horizon_states_ticks_batch(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs, int32_t foot_stride,
+                                              const double* yaw_A, const double* u_full, double* x_pred_out, double* cost_out) {
+    return horizon_states_host_impl(h, n, true, tick, nullptr, R_world, foot_abs, foot_stride, yaw_A, u_full, x_pred_out, cost_out);
 }
 #undef A1_STAGE_BEGIN
 #undef A1_STAGE_DEVICE

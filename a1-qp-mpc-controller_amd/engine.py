@@ -60,7 +60,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_horizon_preview_footholds_batch", "a1mpc_horizon_preview_footholds_batch_device", "a1mpc_control_tick_preview_footholds_device",
+EXPORTS = ["a1mpc_horizon_states_batch", "a1mpc_horizon_states_batch_device", "a1mpc_horizon_states_ticks_batch", "a1mpc_horizon_states_ticks_batch_device",
+           "a1mpc_horizon_preview_footholds_batch", "a1mpc_horizon_preview_footholds_batch_device", "a1mpc_control_tick_preview_footholds_device",
            "a1mpc_pipeline_submit_ticks_strided_device", "a1mpc_default_preview_config", "a1mpc_horizon_preview_batch", "a1mpc_horizon_preview_batch_device", "a1mpc_solve_batch_ticks_strided", "a1mpc_solve_batch_ticks_strided_device",
            "a1mpc_control_tick_preview_device", "a1mpc_set_timing", "a1mpc_default_tick_params", "a1mpc_control_tick_device", "a1mpc_last_control_tick_ms", "a1mpc_last_stage_ms", "a1mpc_sharded_create", "a1mpc_sharded_solve_batch", "a1mpc_sharded_solve_batch_ticks", "a1mpc_sharded_solve_batch_device", "a1mpc_sharded_solve_batch_ticks_device", "a1mpc_sharded_handle",
            "a1mpc_sharded_last_transfer", "a1mpc_sharded_info", "a1mpc_sharded_destroy", "a1mpc_terrain_batch", "a1mpc_form_qp_batch", "a1mpc_solve_batch_strided", "a1mpc_solve_batch_strided_device", "a1mpc_update_config", "a1mpc_warm_start", "a1mpc_get_warm_start", "a1mpc_get_workspace_z", "a1mpc_get_workspace_scaling", "a1mpc_last_warm_start_mode", "a1mpc_set_profiling", "a1mpc_last_stage_cycles", "a1mpc_last_tick_stage_cycles", "a1mpc_update_plan_batch_device", "a1mpc_swing_legs_batch_device", "a1mpc_contact_terrain_batch_device", "a1mpc_leg_state_batch_device",
@@ -177,6 +178,11 @@ def load_library(path=None):
         lib.a1mpc_control_tick_preview_footholds_device.restype = C.c_int
         lib.a1mpc_pipeline_submit_ticks_strided_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32p]
         lib.a1mpc_pipeline_submit_ticks_strided_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_horizon_states_batch"):   # (predicted horizon states and cost; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_horizon_states_batch.argtypes = [vp, i32, dp, dp, dp, dp, i32, dp, dp, dp, dp]; lib.a1mpc_horizon_states_batch.restype = C.c_int
+        lib.a1mpc_horizon_states_batch_device.argtypes = [vp, i32] + [vpp] * 4 + [i32] + [vpp] * 4 + [vpp]; lib.a1mpc_horizon_states_batch_device.restype = C.c_int
+        lib.a1mpc_horizon_states_ticks_batch.argtypes = [vp, i32, dp, dp, dp, i32, dp, dp, dp, dp]; lib.a1mpc_horizon_states_ticks_batch.restype = C.c_int
+        lib.a1mpc_horizon_states_ticks_batch_device.argtypes = [vp, i32] + [vpp] * 3 + [i32] + [vpp] * 4 + [vpp]; lib.a1mpc_horizon_states_ticks_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_last_tick_stage_cycles"):  # (round 5; an older build bound by hand for an A/B may lack it)
         lib.a1mpc_last_tick_stage_cycles.argtypes = [vp, dp, C.POINTER(C.c_int32)]; lib.a1mpc_last_tick_stage_cycles.restype = C.c_int
     lib.a1mpc_set_schedule.argtypes = [vp, i32]; lib.a1mpc_set_schedule.restype = C.c_int
@@ -395,6 +401,45 @@ class Engine:
                                                       None if yaw_A is None else _dp(np.ascontiguousarray(yaw_A, dtype=np.float64)), _dp(grf), _dp(u), _ip(iters), _ip(status))
         _check(self.lib, rc, "a1mpc_solve_batch_ticks_strided")
         return dict(grf=grf, u=u, iters=iters, status=status)
+
+    # ---- what the model does with a force plan: predicted states over the horizon (A_qp x0 + B_qp u of the reference's ConvexMpc members) and the plan's cost ----
+    def horizon_states(self, x0, R, foot, u=None, xref=None, foot_stride=0, yaw_A=None):
+        """dict(x_pred (n, H, 13): x_(t+1) at step t; cost (n, 2): [tracking, effort], or None without xref): a1mpc_horizon_states_batch.  u (n, 12 H) world-frame
+        forces (u_full of a solve), None = zero forces: the free response"""
+        h = self.horizon
+        x0 = _f64(x0, (-1, NS)); n = x0.shape[0]
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12 * h if foot_stride else 12))
+        u = None if u is None else _f64(u, (n, NU * h)); xref = None if xref is None else _f64(xref, (n, NS * h))
+        x_pred = np.zeros((n, h, NS)); cost = None if xref is None else np.zeros((n, 2))
+        rc = self.lib.a1mpc_horizon_states_batch(self._h, n, _dp(x0), _dp(xref), _dp(R), _dp(foot), int(foot_stride),
+                                                 None if yaw_A is None else _dp(np.ascontiguousarray(yaw_A, dtype=np.float64)), _dp(u), _dp(x_pred), _dp(cost))
+        _check(self.lib, rc, "a1mpc_horizon_states_batch")
+        return dict(x_pred=x_pred, cost=cost)
+
+    def horizon_states_ticks(self, tick, R, foot, u=None, foot_stride=0, yaw_A=None, want_cost=True):
+        """the same from the compact tick records (x0 / x_ref built on the device as the ticks solve builds them): a1mpc_horizon_states_ticks_batch"""
+        h = self.horizon
+        tick = _f64(tick, (-1, 22)); n = tick.shape[0]
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12 * h if foot_stride else 12))
+        u = None if u is None else _f64(u, (n, NU * h))
+        x_pred = np.zeros((n, h, NS)); cost = np.zeros((n, 2)) if want_cost else None
+        rc = self.lib.a1mpc_horizon_states_ticks_batch(self._h, n, _dp(tick), _dp(R), _dp(foot), int(foot_stride),
+                                                       None if yaw_A is None else _dp(np.ascontiguousarray(yaw_A, dtype=np.float64)), _dp(u), _dp(x_pred), _dp(cost))
+        _check(self.lib, rc, "a1mpc_horizon_states_ticks_batch")
+        return dict(x_pred=x_pred, cost=cost)
+
+    def horizon_states_device(self, n, d_x0, d_xref, d_R, d_foot, foot_stride, d_u, d_x_pred=None, d_cost=None, d_yaw_A=None, stream=None):
+        """device pointers (torch tensors), asynchronous on `stream`: on the stream of the preceding solve_device it reads that solve's d_u"""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        rc = self.lib.a1mpc_horizon_states_batch_device(self._h, int(n), ptr(d_x0), ptr(d_xref), ptr(d_R), ptr(d_foot), int(foot_stride), ptr(d_yaw_A), ptr(d_u),
+                                                        ptr(d_x_pred), ptr(d_cost), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_horizon_states_batch_device")
+
+    def horizon_states_ticks_device(self, n, d_tick, d_R, d_foot, foot_stride, d_u, d_x_pred=None, d_cost=None, d_yaw_A=None, stream=None):
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        rc = self.lib.a1mpc_horizon_states_ticks_batch_device(self._h, int(n), ptr(d_tick), ptr(d_R), ptr(d_foot), int(foot_stride), ptr(d_yaw_A), ptr(d_u),
+                                                              ptr(d_x_pred), ptr(d_cost), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_horizon_states_ticks_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

@@ -520,6 +520,46 @@ a1mpc_status a1mpc_control_tick_preview_footholds_device(a1mpc_handle h, const a
                                                          const a1mpc_tick_buffers* buffers, int32_t n, void* hip_stream);
 
 /*
+ * What the model does with a force plan: the predicted states over the horizon and the cost of the plan, n problems, on the device.  The reference keeps A_qp and B_qp
+ * as public members of ConvexMpc (S/ConvexMpc.h, filled by calculate_qp_mats, S/ConvexMpc.cpp:181-202); its caller gets the predicted trajectory A_qp x0 + B_qp u and the
+ * tracking cost with one Eigen product each.  These entries replace that use of the two members (the solver here never forms them): x_pred IS A_qp x0 + B_qp u.
+ * The model is exactly the reference's: A_d = I + dt A_c, B_d,t = dt B_c,t (forward Euler, S/ConvexMpc.cpp:110-151), with R_world and the yaw of A_c FROZEN over the
+ * horizon (one A_d for all steps, one world inertia; only the feet may change per step).  With x_0 = x0[i], for t = 0 .. H-1 (H = the handle's horizon, >= 2), every
+ * x_t read before x_(t+1) is written:
+ *   rpy_(t+1) = rpy_t + dt T w_t                         T = [c s 0; -s c 0; 0 0 1], c, s = cos / sin(yaw), yaw = yaw_A[i] or x0[i][2]
+ *   pos_(t+1) = pos_t + dt v_t
+ *   w_(t+1)   = w_t + dt Iw^-1 sum_leg r_(t,leg) x f_(t,leg)     Iw = R I_b R', r = foot_abs (step t with foot_stride 12), f = u_full; legs summed in the order 0 .. 3
+ *   v_(t+1)   = v_t + (dt / m) sum_leg f_(t,leg) + dt [0, 0, x_t[12]]
+ *   x_(t+1)[12] = x_t[12]
+ * Layouts are those of a1mpc_solve_batch_strided / a1mpc_solve_batch_ticks_strided (x0 n x 13, x_ref n x 13H, R_world n x 9 row-major, foot_abs n x 12 or n x 12H,
+ * foot_stride 0 / 12, yaw_A NULL or n, u_full n x 12H world-frame forces = u_full_out of a solve): the inputs and outputs of a solve are passed on unchanged.
+ * dt, q, r, mass, inertia_body and the horizon are the handle's configuration.  u_full == NULL means zero forces: the free response A_qp x0.
+ * out, each may be NULL (not both):
+ *   x_pred_out  n x 13H   step t of problem i at [(i*H + t)*13] holds x_(t+1) -- the index convention of x_ref / mpc_states_d, whose block t is compared with A_d^(t+1) x0
+ *   cost_out    n x 2     [0] = sum_t sum_(k<12) q_k (x_(t+1),k - x_ref_t,k)^2        [1] = sum_t sum_j r_j u_(t,j)^2
+ * With the reference's Q = 2 diag(q), R = 2 diag(r) (S/ConvexMpc.cpp:12-44) these are 1/2 e'Qe and 1/2 u'Ru, so
+ *   cost[0](u) + cost[1](u) - cost[0](0) = 1/2 u'Pu + g'u,
+ * OSQP's objective on the reference's hessian / gradient (S/ConvexMpc.cpp:204-215); cost[0](0) is what a call with u_full == NULL returns.  cost_out needs x_ref.
+ * The _ticks entries take the compact tick record of a1mpc_solve_batch_ticks instead of (x0, x_ref): x0 = [tick[0:12], -9.8] and x_ref_t = base + (slope dt)(t + 1),
+ * built as S/A1RobotControl.cpp:470-488 builds mpc_states_d, with the expressions the solve's set-up uses.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the argument), whether or not a GPU is present: a null handle, n < 0 or n > max_batch, a foot_stride
+ * other than 0 / 12, both outputs NULL, cost_out without x_ref, a null x0 / tick, R_world or foot_abs, a handle of horizon < 2.  n == 0 is A1MPC_OK and launches nothing.
+ * Host pointers; the _device entries take device pointers and are asynchronous on hip_stream (NULL = the handle's): a call on the stream of the preceding
+ * a1mpc_solve_batch_*_device sees its d_u_full_out, so solve -> predicted state -> next tick's x0 chains without a host copy.
+ */
+a1mpc_status a1mpc_horizon_states_batch(a1mpc_handle h, int32_t n, const double* x0, const double* x_ref, const double* R_world,
+                                        const double* foot_abs, int32_t foot_stride, const double* yaw_A, const double* u_full,
+                                        double* x_pred_out, double* cost_out);
+a1mpc_status a1mpc_horizon_states_batch_device(a1mpc_handle h, int32_t n, const double* d_x0, const double* d_x_ref, const double* d_R_world,
+                                               const double* d_foot_abs, int32_t foot_stride, const double* d_yaw_A, const double* d_u_full,
+                                               double* d_x_pred_out, double* d_cost_out, void* hip_stream);
+a1mpc_status a1mpc_horizon_states_ticks_batch(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs,
+                                              int32_t foot_stride, const double* yaw_A, const double* u_full, double* x_pred_out, double* cost_out);
+a1mpc_status a1mpc_horizon_states_ticks_batch_device(a1mpc_handle h, int32_t n, const double* d_tick, const double* d_R_world, const double* d_foot_abs,
+                                                     int32_t foot_stride, const double* d_yaw_A, const double* d_u_full, double* d_x_pred_out,
+                                                     double* d_cost_out, void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
