@@ -368,6 +368,51 @@ __global__ __launch_bounds__(256) void a1mpc_horizon_preview_footholds_kernel(co
     if (live) preview_feet<true>(a, b, leg, H, m);
 }
 
+// ---- balance PD wrench (a1mpc_balance_wrench_batch): root_acc of the reference's stance controller of type 0, S/A1RobotControl.cpp:379-391 with the euler error and its
+// yaw wrap of :325-332 -- what a1mpc_balance_solve_batch takes as its first input.  One lane per robot, element-wise, HBM-bound: 27 doubles in, 6 out.  Every load of a
+// robot is issued before the first operation, every store behind the last.  Plain C++ without intrinsics (the CPU suite compiles this section for the host,
+// tests/emu/balance_wrench_host.py); contraction off and only IEEE add / subtract / multiply, every 3-term sum left to right: the result is the reference
+// arithmetic's bit for bit, whatever the batch size.  A NaN input gives NaN in its own robot's row only (a NaN yaw error takes neither branch of the wrap).
+struct WrenchArgs {
+    int32_t n;
+    double kp_lin[3], kd_lin[3], kp_ang[3], kd_ang[3], mass;
+    const double *pos_d, *pos, *lin_vel_d, *lin_vel, *euler_d, *euler, *ang_vel_d, *ang_vel, *R;   // n x 3 each, R n x 9 row-major; *_d velocities in the body frame
+    double* root_acc;                                                                              // n x 6
+};
+__global__ __launch_bounds__(256) void a1mpc_balance_wrench_kernel(const WrenchArgs a) {
+#pragma clang fp contract(off)
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= a.n) return;
+    double pd[3], p[3], vd[3], v[3], ed[3], e[3], wd[3], w[3], R[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        pd[i] = a.pos_d[b * 3 + i]; p[i] = a.pos[b * 3 + i]; vd[i] = a.lin_vel_d[b * 3 + i]; v[i] = a.lin_vel[b * 3 + i];
+        ed[i] = a.euler_d[b * 3 + i]; e[i] = a.euler[b * 3 + i]; wd[i] = a.ang_vel_d[b * 3 + i]; w[i] = a.ang_vel[b * 3 + i];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = a.R[b * 9 + k];
+    double ee[3], t2[3], acc[6];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ee[i] = ed[i] - e[i];
+    if (ee[2] > 3.1415926 * 1.5) ee[2] = ed[2] - 3.1415926 * 2 - e[2];                              // :328-332 (strict comparisons: a yaw error ON the mark is kept)
+    else if (ee[2] < -3.1415926 * 1.5) ee[2] = ed[2] + 3.1415926 * 2 - e[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double t = vd[i] - (R[0 * 3 + i] * v[0] + R[1 * 3 + i] * v[1] + R[2 * 3 + i] * v[2]);   // root_lin_vel_d - R' root_lin_vel
+        t2[i] = a.kd_lin[i] * t;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        acc[i] = a.kp_lin[i] * (pd[i] - p[i]);                                                       // :380
+        acc[i] = acc[i] + (R[i * 3 + 0] * t2[0] + R[i * 3 + 1] * t2[1] + R[i * 3 + 2] * t2[2]);       // :382-383
+        acc[3 + i] = a.kp_ang[i] * ee[i];                                                            // :385
+        acc[3 + i] = acc[3 + i] + a.kd_ang[i] * (wd[i] - (R[0 * 3 + i] * w[0] + R[1 * 3 + i] * w[1] + R[2 * 3 + i] * w[2]));   // :386-387
+    }
+    acc[2] = acc[2] + a.mass * 9.8;                                                                  // :391
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a.root_acc[b * 6 + k] = acc[k];
+}
+
 // ---- predicted horizon states and the cost of a force plan (a1mpc_horizon_states_batch): x_(t+1) = A_d x_t + B_d,t u_t rolled out from x0, i.e. A_qp x0 + B_qp u of the
 // reference's public members (S/ConvexMpc.h, S/ConvexMpc.cpp:181-202) without forming either, and the two sums 1/2 e'Qe, 1/2 u'Ru.  Memory-bound: 25H + 34 doubles in,
 // 13H + 2 out per QP.
@@ -800,6 +845,7 @@ struct a1mpc_handle_s {
     double* d_tickrec = nullptr;    // a1mpc_control_tick_device: n x 22 tick records + 3 doubles (km_foot), allocated on first use
     uint32_t* d_pv_sched = nullptr; // a1mpc_control_tick_preview_device: n x H words, the horizon's contact schedule (allocated on first use)
     double* d_pv_foot = nullptr;    // ... and n x 12H per-step feet (allocated on first use)
+    double* d_bal_acc = nullptr;    // a1mpc_control_tick_balance_device: n x 6 root_acc where the caller passes no buffer of its own (allocated on first use)
     double *d_hs_u = nullptr, *d_hs_x = nullptr;   // a1mpc_horizon_states_batch (host pointers): n x 12H forces in, n x 13H predicted states out (allocated on first use)
     int32_t ekf_ready_n = 0;        // robots 0 .. ekf_ready_n - 1 have had their filter initialised (the init kernel is not launched for them again)
     // staging of the host-pointer entries of the caller-side stages, allocated on first use (ensure_aux; handed out by Staging)
@@ -929,10 +975,12 @@ __device__ inline void sym3_pinv(const double* m, double* out) {  // pseudo-inve
 }
 // a robot's inputs of one tick: loaded BEFORE its record is staged, so that they travel with the record instead of after it (round 6: until then they were loaded behind the
 // staging barrier, the ring sectors behind them, root_pos_z behind the plane fit and the terrain ring's word behind that -- five exposures to the memory latency per robot, now two)
+// contacts_only (a literal at every call: folded where these bodies are inlined): the contact block alone, a1mpc_contacts_batch -- root_pos_z is not read, and neither
+// the terrain-angle filter, the plane fit, root_euler_d nor a terrain output is touched (S/A1RobotControl.cpp:335: "only do terrain adaptation in MPC")
 struct CtInputs { double gc[4], ff[4], fp[12], rz; uint8_t plan[4]; };
-__device__ __forceinline__ CtInputs contact_terrain_inputs(const ContactArgs& a, const int64_t b) {
+__device__ __forceinline__ CtInputs contact_terrain_inputs(const ContactArgs& a, const int64_t b, const bool contacts_only = false) {
     CtInputs in;
-    in.rz = a.root_pos_z[b * a.z_stride];
+    in.rz = contacts_only ? 0.0 : a.root_pos_z[b * a.z_stride];
     if (!a.recent_in) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { in.gc[i] = a.gait_counter[b * 4 + i]; in.ff[i] = a.foot_force[b * 4 + i]; in.plan[i] = a.plan_contacts[b * 4 + i]; }
@@ -942,11 +990,11 @@ __device__ __forceinline__ CtInputs contact_terrain_inputs(const ContactArgs& a,
     return in;
 }
 // one robot's tick on its record `st` (the kernel hands in the record's LDS image; the terrain-only entry and the host-compiled test double the record itself)
-__device__ __forceinline__ void contact_terrain_robot_in(const ContactArgs& a, const int64_t b, CtRecord* st, const CtInputs& in) {
+__device__ __forceinline__ void contact_terrain_robot_in(const ContactArgs& a, const int64_t b, CtRecord* st, const CtInputs& in, const bool contacts_only = false) {
 #pragma clang fp contract(off)
     double rc[12];
     // the terrain-angle filter's word under its cursor is read here, with the leg rings' sectors: everything a tick reads in place is in flight before anything is computed
-    const bool standing = in.rz > 0.1;
+    const bool standing = !contacts_only && in.rz > 0.1;
     const int tcount = st->rb.count, thead = st->rb.head;
     double* tr = a.terrain_ring + thead * a.stride + b;
     const double tr_old = (standing && tcount >= kTerrainWindow) ? *tr : 0.0;
@@ -1005,6 +1053,7 @@ __device__ __forceinline__ void contact_terrain_robot_in(const ContactArgs& a, c
 #pragma unroll
         for (int k = 0; k < 12; ++k) a.recent_out[b * 12 + k] = rc[k];
     }
+    if (contacts_only) return;
     double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, rhs[3] = {0, 0, 0}, P3[9], co[3];   // :566-582  a = pinv(W'W) W' z
     for (int i = 0; i < 4; ++i) {
         const double w[3] = {1.0, rc[3 * i + 0], rc[3 * i + 1]};
@@ -1073,6 +1122,28 @@ __global__ __launch_bounds__(64) void a1mpc_contact_terrain_kernel(const Contact
 #pragma unroll
     for (int i = 0; i < kCtUnits; ++i) { const int o = i * 64 + lane, r = o / kCtUnits, w = o - r * kCtUnits; if (o < cnt * kCtUnits) dst[o] = *reinterpret_cast<const uint4*>(img + r * kCtLdsStride + w * 16); }
 }
+// The contact block alone (a1mpc_contacts_batch, the balance control tick): the kernel above with contacts_only folded in -- the same staging of the records through LDS
+// around the same per-robot body, which returns in front of the plane fit.  A kernel of its own, so that the kernel above keeps its code to the instruction
+__global__ __launch_bounds__(64) void a1mpc_contacts_kernel(const ContactArgs a) {
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * 64;
+    const int lane = threadIdx.x;
+    const int64_t b = base + lane;
+    __shared__ __attribute__((aligned(16))) unsigned char img[64 * kCtLdsStride];
+    const int cnt = a.n - base < 64 ? static_cast<int>(a.n - base) : 64;
+    const CtInputs in = contact_terrain_inputs(a, b < a.n ? b : a.n - 1, true);
+    const uint4* src = reinterpret_cast<const uint4*>(a.rec + base);
+    uint4 v[kCtUnits];
+#pragma unroll
+    for (int i = 0; i < kCtUnits; ++i) { const int o = i * 64 + lane; v[i] = o < cnt * kCtUnits ? src[o] : uint4{0, 0, 0, 0}; }
+#pragma unroll
+    for (int i = 0; i < kCtUnits; ++i) { const int o = i * 64 + lane, r = o / kCtUnits, w = o - r * kCtUnits; *reinterpret_cast<uint4*>(img + r * kCtLdsStride + w * 16) = v[i]; }
+    __syncthreads();
+    if (b < a.n) contact_terrain_robot_in(a, b, reinterpret_cast<CtRecord*>(img + lane * kCtLdsStride), in, true);
+    __syncthreads();
+    uint4* dst = reinterpret_cast<uint4*>(a.rec + base);
+#pragma unroll
+    for (int i = 0; i < kCtUnits; ++i) { const int o = i * 64 + lane, r = o / kCtUnits, w = o - r * kCtUnits; if (o < cnt * kCtUnits) dst[o] = *reinterpret_cast<const uint4*>(img + r * kCtLdsStride + w * 16); }
+}
 // the handle's contact state: records, then the leg rings, then the terrain rings (zero = every filter empty)
 static a1mpc_status ensure_contact_state(a1mpc_handle h, hipStream_t s) {
     if (h->d_ct_state) return A1MPC_OK;
@@ -1099,6 +1170,12 @@ static ContactArgs make_contact_args(a1mpc_handle h, const a1mpc_contact_config&
 }
 static void launch_contact_terrain(const ContactArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(a1mpc_contact_terrain_kernel, dim3(static_cast<unsigned>((a.n + 63) / 64)), dim3(64), 0, s, a);
+}
+// the contact block alone on the handle's contact state: no root_pos_z, no pitch, no terrain output, and the terrain-angle filter stays as it is
+static void launch_contacts(a1mpc_handle h, const a1mpc_contact_config& cfg, int32_t n, const double* gait_counter, const uint8_t* plan_contacts, const double* foot_force,
+                            const double* foot_pos_abs, uint8_t* contacts, double* recent_out, hipStream_t s) {
+    const ContactArgs a = make_contact_args(h, cfg, n, gait_counter, plan_contacts, foot_force, foot_pos_abs, nullptr, nullptr, contacts, recent_out, nullptr);
+    hipLaunchKernelGGL(a1mpc_contacts_kernel, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, s, a);
 }
 
 // ---- what the entry points of the caller-side stages share.  A stage has a launcher (launch_<stage>: scalars and DEVICE pointers in, the args struct filled and the
@@ -1906,6 +1983,92 @@ a1mpc_status a1mpc_joint_torques_batch_device(a1mpc_handle h, int32_t n, const u
     return A1MPC_OK;
 }
 
+// ---- the caller side of the balance-QP stance controller (stance_leg_control_type 0): the contact block alone and the PD wrench ----
+// the contact block of generate_swing_legs_ctrl without the terrain fit (S/A1RobotControl.cpp:256-282; :335 skips the terrain block for this controller)
+a1mpc_status a1mpc_contacts_batch(a1mpc_handle h, const a1mpc_contact_config* cfg, int32_t n, const double* gait_counter, const uint8_t* plan_contacts,
+                                  const double* foot_force, const double* foot_pos_abs, uint8_t* contacts_out, double* foot_pos_recent_contact_out) {
+    A1_STAGE_BEGIN(cfg && gait_counter && plan_contacts && foot_force && foot_pos_abs && contacts_out && foot_pos_recent_contact_out,
+                   "null config or input/output pointer", nullptr);
+    Staging sg(h, n, s);
+    if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
+    const double *d_gc = sg.in(gait_counter, 4), *d_ff = sg.in(foot_force, 4), *d_fp = sg.in(foot_pos_abs, 12);
+    const uint8_t* d_pc = sg.in(plan_contacts, 4);
+    uint8_t* d_ct = sg.out(contacts_out, 4);
+    double* d_rec = sg.out(foot_pos_recent_contact_out, 12);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_contacts(h, *cfg, n, d_gc, d_pc, d_ff, d_fp, d_ct, d_rec, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_contacts_batch_device(a1mpc_handle h, const a1mpc_contact_config* cfg, int32_t n, const double* gait_counter, const uint8_t* plan_contacts,
+                                         const double* foot_force, const double* foot_pos_abs, uint8_t* contacts_out, double* foot_pos_recent_contact_out,
+                                         void* hip_stream) {
+    A1_STAGE_BEGIN(cfg && gait_counter && plan_contacts && foot_force && foot_pos_abs && contacts_out && foot_pos_recent_contact_out,
+                   "null config or input/output pointer", hip_stream);
+    if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
+    A1_STAGE_LAUNCH(launch_contacts(h, *cfg, n, gait_counter, plan_contacts, foot_force, foot_pos_abs, contacts_out, foot_pos_recent_contact_out, s));
+    return A1MPC_OK;
+}
+
+void a1mpc_default_balance_gains(a1mpc_balance_gains* g) {
+    if (!g) return;
+    const double kpl[3] = {1000.0, 1000.0, 1000.0}, kdl[3] = {200.0, 70.0, 120.0}, kpa[3] = {650.0, 35.0, 1.0}, kda[3] = {4.5, 4.5, 30.0};   // S/A1CtrlStates.h:117-120
+    std::memcpy(g->kp_linear, kpl, sizeof kpl); std::memcpy(g->kd_linear, kdl, sizeof kdl);
+    std::memcpy(g->kp_angular, kpa, sizeof kpa); std::memcpy(g->kd_angular, kda, sizeof kda);
+}
+static const char* invalid_balance_gains(const a1mpc_balance_gains* g) {
+    if (!g) return "null a1mpc_balance_gains";
+    if (!all_finite(g->kp_linear, 3) || !all_finite(g->kd_linear, 3) || !all_finite(g->kp_angular, 3) || !all_finite(g->kd_angular, 3))
+        return "non-finite gain in a1mpc_balance_gains";
+    return nullptr;
+}
+static void launch_wrench(a1mpc_handle h, const a1mpc_balance_gains& g, int32_t n, const double* root_pos_d, const double* root_pos, const double* root_lin_vel_d,
+                          const double* root_lin_vel, const double* root_euler_d, const double* root_euler, const double* root_ang_vel_d, const double* root_ang_vel,
+                          const double* R_world, double* root_acc, hipStream_t s) {
+    WrenchArgs a;
+    a.n = n; a.mass = h->cfg.mass;
+    for (int i = 0; i < 3; ++i) { a.kp_lin[i] = g.kp_linear[i]; a.kd_lin[i] = g.kd_linear[i]; a.kp_ang[i] = g.kp_angular[i]; a.kd_ang[i] = g.kd_angular[i]; }
+    a.pos_d = root_pos_d; a.pos = root_pos; a.lin_vel_d = root_lin_vel_d; a.lin_vel = root_lin_vel; a.euler_d = root_euler_d; a.euler = root_euler;
+    a.ang_vel_d = root_ang_vel_d; a.ang_vel = root_ang_vel; a.R = R_world; a.root_acc = root_acc;
+    hipLaunchKernelGGL(a1mpc_balance_wrench_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 255) / 256)), dim3(256), 0, s, a);
+}
+// which of the wrench's arrays is null, or null (none)
+static const char* null_wrench_array(const double* root_pos_d, const double* root_pos, const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d,
+                                     const double* root_euler, const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world, const double* root_acc_out) {
+    const struct { const double* p; const char* what; } arrays[] = {{root_pos_d, "null root_pos_d"}, {root_pos, "null root_pos"}, {root_lin_vel_d, "null root_lin_vel_d"},
+        {root_lin_vel, "null root_lin_vel"}, {root_euler_d, "null root_euler_d"}, {root_euler, "null root_euler"}, {root_ang_vel_d, "null root_ang_vel_d"},
+        {root_ang_vel, "null root_ang_vel"}, {R_world, "null R_world"}, {root_acc_out, "null root_acc_out"}};
+    for (const auto& q : arrays) if (!q.p) return q.what;
+    return nullptr;
+}
+#define A1_WRENCH_BEGIN(hip_stream)                                                                                                     \
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");                                                                      \
+    if (const char* bad = invalid_balance_gains(gains)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);                                    \
+    if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");                                                                    \
+    if (const char* bad = null_wrench_array(root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, \
+                                            root_ang_vel, R_world, root_acc_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);          \
+    A1_STAGE_DEVICE(hip_stream)
+a1mpc_status a1mpc_balance_wrench_batch(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* root_pos_d, const double* root_pos,
+                                        const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d, const double* root_euler,
+                                        const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world, double* root_acc_out) {
+    A1_WRENCH_BEGIN(nullptr);
+    Staging sg(h, n, s);
+    const double *d_pd = sg.in(root_pos_d, 3), *d_p = sg.in(root_pos, 3), *d_vd = sg.in(root_lin_vel_d, 3), *d_v = sg.in(root_lin_vel, 3), *d_ed = sg.in(root_euler_d, 3),
+                 *d_e = sg.in(root_euler, 3), *d_wd = sg.in(root_ang_vel_d, 3), *d_w = sg.in(root_ang_vel, 3), *d_R = sg.in(R_world, 9);
+    double* d_acc = sg.out(root_acc_out, 6);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_wrench(h, *gains, n, d_pd, d_p, d_vd, d_v, d_ed, d_e, d_wd, d_w, d_R, d_acc, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_balance_wrench_batch_device(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* root_pos_d, const double* root_pos,
+                                               const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d, const double* root_euler,
+                                               const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world, double* root_acc_out, void* hip_stream) {
+    A1_WRENCH_BEGIN(hip_stream);
+    A1_STAGE_LAUNCH(launch_wrench(h, *gains, n, root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, root_ang_vel, R_world,
+                                  root_acc_out, s));
+    return A1MPC_OK;
+}
+#undef A1_WRENCH_BEGIN
+
 const char* a1mpc_status_string(a1mpc_status s) {
     switch (s) {
         case A1MPC_OK: return "ok";
@@ -1927,7 +2090,7 @@ void a1mpc_destroy(a1mpc_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_tab, h->d_tab1, h->d_x0, h->d_xref, h->d_R, h->d_foot, h->d_aux, h->d_Rz, h->d_contact, h->d_grf,
-                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x};
+                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x, h->d_bal_acc};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -3080,6 +3243,32 @@ a1mpc_status a1mpc_solve_batch_ticks_strided(a1mpc_handle h, int32_t n, const do
     host_collect(h, N, 12 * H, grf_body_out, u_full_out, iters_out, status_out);
     return A1MPC_OK;
 }
+// the balance QP as the H = 1 member of the kernel family: dt = 0, wrench weights (torque first) in q2[6:12], R on the diagonal, the handle's OSQP settings with the
+// warm start off.  The caller sets the input / output pointers
+static KernelArgs balance_kernel_args(a1mpc_handle h, const a1mpc_balance_config& qp, int32_t n) {
+    KernelArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.P = h->dp;
+    a.P.dt = 0.0; a.P.mu = qp.mu; a.P.fz_min = qp.F_min; a.P.fz_max = qp.F_max; a.P.warm_start = 0;
+    for (int i = 0; i < 12; ++i) { a.P.q2[i] = 0.0; a.P.r2[i] = qp.R; }
+    for (int k = 0; k < 3; ++k) { a.P.q2[6 + k] = qp.Q[3 + k]; a.P.q2[9 + k] = qp.Q[k]; }
+    a.tab = h->d_tab1; a.n = n; a.nfact = h->d_nfact;
+    return a;
+}
+// the balance launch on device pointers between the handle's timing events (a1mpc_last_kernel_ms, a1mpc_last_nfact); the caller has ordered the stream and marks it
+static a1mpc_status launch_balance_device(a1mpc_handle h, const a1mpc_balance_config& qp, int32_t n, const double* root_acc, const double* R_world, const double* R_z,
+                                          const double* foot_abs, const uint8_t* contact, double* grf_body_out, double* f_world_out, int32_t* iters_out,
+                                          int32_t* status_out, hipStream_t s) {
+    KernelArgs a = balance_kernel_args(h, qp, n);
+    a.root_acc = root_acc; a.R = R_world; a.Rz = R_z; a.foot = foot_abs; a.contact = contact;
+    a.grf = grf_body_out; a.u_full = f_world_out; a.iters = iters_out; a.status = status_out;
+    if (h->timing) A1_HIP(hipEventRecord(h->ev0, s));
+    h->staged = false;
+    if (a1mpc_status st = launch<1, kModeBalance>(a, s); st != A1MPC_OK) return st;
+    if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
+    h->timed = h->timing;
+    return A1MPC_OK;
+}
 a1mpc_status a1mpc_balance_solve_batch(a1mpc_handle h, const a1mpc_balance_config* qp, int32_t n, const double* root_acc,
                                        const double* R_world, const double* R_z, const double* foot_abs, const uint8_t* contact,
                                        double* grf_body_out, double* f_world_out, int32_t* iters_out, int32_t* status_out) {
@@ -3093,14 +3282,7 @@ a1mpc_status a1mpc_balance_solve_batch(a1mpc_handle h, const a1mpc_balance_confi
     const size_t N = n;
     hipStream_t s = h->stream;
     A1_ORDER(h, s);
-    KernelArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.P = h->dp;
-    // the H = 1 member of the family: dt = 0, wrench weights (torque first) in q2[6:12], R on the diagonal
-    a.P.dt = 0.0; a.P.mu = qp->mu; a.P.fz_min = qp->F_min; a.P.fz_max = qp->F_max; a.P.warm_start = 0;
-    for (int i = 0; i < 12; ++i) { a.P.q2[i] = 0.0; a.P.r2[i] = qp->R; }
-    for (int k = 0; k < 3; ++k) { a.P.q2[6 + k] = qp->Q[3 + k]; a.P.q2[9 + k] = qp->Q[k]; }
-    a.tab = h->d_tab1; a.n = n; a.nfact = h->d_nfact;
+    KernelArgs a = balance_kernel_args(h, *qp, n);
     size_t armed = 0;
     if (small_batch(h, n)) {   // a handful of QPs (the drop-in's compute_grf with stance_leg_control_type = 0 is n = 1)
         const PinnedIn in = pin_inputs(h, {{root_acc, N * 6 * sizeof(double)}, {R_world, N * 9 * sizeof(double)}, {R_z, N * 9 * sizeof(double)},
@@ -3135,6 +3317,85 @@ a1mpc_status a1mpc_balance_solve_batch(a1mpc_handle h, const a1mpc_balance_confi
     if (iters_out) A1_HIP(hipMemcpyAsync(iters_out, h->d_iters, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (status_out) A1_HIP(hipMemcpyAsync(status_out, h->d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     A1_HIP(hipStreamSynchronize(s));
+    return A1MPC_OK;
+}
+// a1mpc_balance_solve_batch on device pointers: asynchronous on hip_stream (NULL = the handle's), no host synchronisation, no pinned small-batch block -- the same
+// argument fill and the same launch, the same bits
+a1mpc_status a1mpc_balance_solve_batch_device(a1mpc_handle h, const a1mpc_balance_config* qp, int32_t n, const double* d_root_acc, const double* d_R_world,
+                                              const double* d_R_z, const double* d_foot_abs, const uint8_t* d_contact, double* d_grf_body_out, double* d_f_world_out,
+                                              int32_t* d_iters_out, int32_t* d_status_out, void* hip_stream) {
+    if (!h || !qp) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle/config");
+    if (const char* why = invalid_balance_config(*qp)) return fail(A1MPC_ERR_INVALID_ARGUMENT, why);
+    if (n < 0 || !d_root_acc || !d_R_world || !d_R_z || !d_foot_abs || !d_contact || !d_grf_body_out)
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, "null input/output pointer");
+    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
+    if (n == 0) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
+    A1_ORDER(h, s);
+    if (a1mpc_status st = launch_balance_device(h, *qp, n, d_root_acc, d_R_world, d_R_z, d_foot_abs, d_contact, d_grf_body_out, d_f_world_out, d_iters_out, d_status_out, s);
+        st != A1MPC_OK) return st;
+    A1_MARK(h, s);
+    return A1MPC_OK;
+}
+
+// One control tick of n robots on the balance-QP stance controller (stance_leg_control_type 0) in ONE call: stages 1-4 of control_tick_impl (leg state, EKF, plan, swing
+// legs), the contact block WITHOUT the terrain fit (S/A1RobotControl.cpp:335) and without a tick record, then compute_grf's other branch -- the PD wrench (:379-391), the
+// 12-variable QP (:393-444) -- and compute_joint_torques (:289-319) as a launch of its own, back to back on one stream, no host round trip.  Bit-identical to chaining
+// a1mpc_leg_state_batch_device, a1mpc_ekf_update_batch_device, a1mpc_update_plan_batch_device, a1mpc_swing_legs_batch_device, a1mpc_contacts_batch_device,
+// a1mpc_balance_wrench_batch_device, a1mpc_balance_solve_batch_device, a1mpc_joint_torques_batch_device.  buffers->root_pos_d_z and ->terrain_angle are not used (either
+// may be null), ->root_euler_d is read only; any horizon of the handle will do
+a1mpc_status a1mpc_control_tick_balance_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_balance_tick* bt, const a1mpc_tick_buffers* bf, int32_t n,
+                                               void* hip_stream) {
+    if (!h || !p || !bt || !bf) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle / params / balance tick / buffers");
+    if (const char* bad = invalid_balance_gains(&bt->gains)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (const char* why = invalid_balance_config(bt->qp)) return fail(A1MPC_ERR_INVALID_ARGUMENT, why);
+    if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
+    if (n > h->max_batch) return fail(A1MPC_ERR_BATCH_TOO_LARGE, "n > max_batch given to a1mpc_create");
+    if (!bt->root_pos_d) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null a1mpc_balance_tick.root_pos_d");
+    const void* need[] = {bf->joint_pos, bf->joint_vel, bf->R_world, bf->R_z, bf->root_euler, bf->root_ang_vel, bf->imu_acc, bf->imu_ang_vel, bf->foot_force, bf->movement_mode,
+                          bf->mpc_active, bf->root_lin_vel_d, bf->root_ang_vel_d, bf->gait_counter_speed, bf->torques_gravity, bf->gait_counter, bf->foot_pos_start,
+                          bf->foot_pos_rel_last_time, bf->foot_pos_target_last_time, bf->root_euler_d, bf->joint_torques, bf->root_pos, bf->root_lin_vel, bf->estimated_contacts,
+                          bf->plan_contacts, bf->contacts, bf->foot_pos_rel, bf->j_foot_blocks, bf->foot_vel_rel, bf->foot_pos_abs, bf->foot_pos_target_rel, bf->foot_pos_cur,
+                          bf->foot_forces_kin, bf->foot_pos_recent_contact, bf->grf};
+    for (const void* q : need) if (!q) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null device pointer in a1mpc_tick_buffers (only the optional outputs, root_pos_d_z and terrain_angle may be null)");
+    if (!(p->control_dt > 0)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "control_dt <= 0");
+    if (n == 0) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
+    A1_ORDER(h, s);
+    double* root_acc = bt->root_acc;
+    if (!root_acc) {   // the handle's own, allocated once
+        if (!h->d_bal_acc) A1_HIP(hipMalloc(&h->d_bal_acc, static_cast<size_t>(h->max_batch) * 6 * sizeof(double)));
+        root_acc = h->d_bal_acc;
+    }
+    if (a1mpc_status st = ensure_ekf_state(h, s); st != A1MPC_OK) return st;
+    if (a1mpc_status st = ensure_contact_state(h, s); st != A1MPC_OK) return st;
+    if (h->timing) A1_HIP(hipEventRecord(h->ev_tick0, s));   // (ev_tick0 .. ev_tick1 = the whole tick; ev0 .. ev1 = the balance launch)
+    // 1. leg state, 2. EKF, 3. update_plan + 4. swing legs: the launches of control_tick_impl
+    launch_leg(n, p->rho_fix, p->rho_opt, bf->joint_pos, bf->joint_vel, bf->R_world, bf->root_pos, bf->root_lin_vel, bf->foot_pos_rel, bf->j_foot_blocks, bf->foot_vel_rel,
+               bf->foot_pos_abs, bf->foot_vel_abs, bf->foot_pos_world, bf->foot_vel_world, s);
+    if (a1mpc_status st = launch_ekf(h, n, p->control_dt, p->assume_flat_ground, bf->movement_mode, bf->foot_force, bf->R_world, bf->imu_acc, bf->imu_ang_vel, bf->foot_pos_rel,
+                                     bf->foot_vel_rel, bf->root_pos, bf->root_lin_vel, bf->estimated_contacts, s); st != A1MPC_OK) return st;
+    hipLaunchKernelGGL(a1mpc_plan_swing_kernel, leg_lane_grid(n), dim3(256), 0, s,
+                       make_plan_args(p->gait, n, bf->movement_mode, bf->gait_counter, bf->gait_counter_speed, bf->root_lin_vel, bf->R_z, bf->R_world, bf->root_pos, bf->root_lin_vel_d,
+                                      bf->plan_contacts, bf->foot_pos_target_rel, bf->foot_pos_target_abs, bf->foot_pos_target_world),
+                       make_swing_args(n, p->gait.counter_per_swing, p->control_dt, p->kp_foot, p->kd_foot, bf->R_z, bf->foot_pos_abs, bf->gait_counter, bf->foot_pos_target_rel,
+                                       bf->foot_pos_start, bf->foot_pos_rel_last_time, bf->foot_pos_target_last_time, bf->foot_pos_cur, bf->foot_forces_kin));
+    // 5. the contact block alone, 6. the PD wrench from this tick's estimate
+    launch_contacts(h, p->contact, n, bf->gait_counter, bf->plan_contacts, bf->foot_force, bf->foot_pos_abs, bf->contacts, bf->foot_pos_recent_contact, s);
+    launch_wrench(h, bt->gains, n, bt->root_pos_d, bf->root_pos, bf->root_lin_vel_d, bf->root_lin_vel, bf->root_euler_d, bf->root_euler, bf->root_ang_vel_d, bf->root_ang_vel,
+                  bf->R_world, root_acc, s);
+    A1_HIP(hipGetLastError());
+    // 7. the balance QP, 8. joint torques
+    if (a1mpc_status st = launch_balance_device(h, bt->qp, n, root_acc, bf->R_world, bf->R_z, bf->foot_pos_abs, bf->contacts, bf->grf, bt->f_world, bf->iters, bf->status, s);
+        st != A1MPC_OK) return st;
+    launch_torque(n, bf->mpc_active, bf->contacts, bf->j_foot_blocks, bf->grf, bf->foot_forces_kin, p->km_foot, bf->torques_gravity, bf->joint_torques, s);
+    A1_HIP(hipGetLastError());
+    h->tick_fused = false;
+    if (h->timing) A1_HIP(hipEventRecord(h->ev_tick1, s));
+    h->tick_timed = h->timing;
+    A1_MARK(h, s);
     return A1MPC_OK;
 }
 

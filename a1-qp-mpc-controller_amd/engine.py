@@ -49,6 +49,14 @@ class PreviewConfig(C.Structure):  # a1mpc_preview_config: the gait-aware horizo
     _fields_ = [("contact_schedule", C.c_int32), ("foot_preview", C.c_int32), ("ticks_per_step", C.c_int32)]
 
 
+class BalanceGains(C.Structure):  # a1mpc_balance_gains: the PD gains of the balance controller's wrench (S/A1CtrlStates.h:117-120)
+    _fields_ = [("kp_linear", C.c_double * 3), ("kd_linear", C.c_double * 3), ("kp_angular", C.c_double * 3), ("kd_angular", C.c_double * 3)]
+
+
+class BalanceTick(C.Structure):  # a1mpc_balance_tick: what a1mpc_control_tick_balance_device takes beside TickParams / TickBuffers (device pointers)
+    _fields_ = [("gains", BalanceGains), ("qp", BalanceConfig), ("root_pos_d", C.c_void_p), ("root_acc", C.c_void_p), ("f_world", C.c_void_p)]
+
+
 TICK_BUFFER_FIELDS = ("joint_pos", "joint_vel", "R_world", "R_z", "root_euler", "root_ang_vel", "imu_acc", "imu_ang_vel", "foot_force", "movement_mode", "mpc_active",
                       "root_lin_vel_d", "root_ang_vel_d", "root_pos_d_z", "gait_counter_speed", "torques_gravity", "gait_counter", "foot_pos_start", "foot_pos_rel_last_time",
                       "foot_pos_target_last_time", "root_euler_d", "joint_torques", "root_pos", "root_lin_vel", "estimated_contacts", "plan_contacts", "contacts", "foot_pos_rel",
@@ -60,7 +68,9 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_horizon_states_batch", "a1mpc_horizon_states_batch_device", "a1mpc_horizon_states_ticks_batch", "a1mpc_horizon_states_ticks_batch_device",
+EXPORTS = ["a1mpc_default_balance_gains", "a1mpc_balance_wrench_batch", "a1mpc_balance_wrench_batch_device", "a1mpc_balance_solve_batch_device", "a1mpc_contacts_batch",
+           "a1mpc_contacts_batch_device", "a1mpc_control_tick_balance_device",
+           "a1mpc_horizon_states_batch", "a1mpc_horizon_states_batch_device", "a1mpc_horizon_states_ticks_batch", "a1mpc_horizon_states_ticks_batch_device",
            "a1mpc_horizon_preview_footholds_batch", "a1mpc_horizon_preview_footholds_batch_device", "a1mpc_control_tick_preview_footholds_device",
            "a1mpc_pipeline_submit_ticks_strided_device", "a1mpc_default_preview_config", "a1mpc_horizon_preview_batch", "a1mpc_horizon_preview_batch_device", "a1mpc_solve_batch_ticks_strided", "a1mpc_solve_batch_ticks_strided_device",
            "a1mpc_control_tick_preview_device", "a1mpc_set_timing", "a1mpc_default_tick_params", "a1mpc_control_tick_device", "a1mpc_last_control_tick_ms", "a1mpc_last_stage_ms", "a1mpc_sharded_create", "a1mpc_sharded_solve_batch", "a1mpc_sharded_solve_batch_ticks", "a1mpc_sharded_solve_batch_device", "a1mpc_sharded_solve_batch_ticks_device", "a1mpc_sharded_handle",
@@ -183,6 +193,15 @@ def load_library(path=None):
         lib.a1mpc_horizon_states_batch_device.argtypes = [vp, i32] + [vpp] * 4 + [i32] + [vpp] * 4 + [vpp]; lib.a1mpc_horizon_states_batch_device.restype = C.c_int
         lib.a1mpc_horizon_states_ticks_batch.argtypes = [vp, i32, dp, dp, dp, i32, dp, dp, dp, dp]; lib.a1mpc_horizon_states_ticks_batch.restype = C.c_int
         lib.a1mpc_horizon_states_ticks_batch_device.argtypes = [vp, i32] + [vpp] * 3 + [i32] + [vpp] * 4 + [vpp]; lib.a1mpc_horizon_states_ticks_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
+        lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
+        lib.a1mpc_balance_wrench_batch_device.argtypes = [vp, C.POINTER(BalanceGains), i32] + [vpp] * 10 + [vpp]; lib.a1mpc_balance_wrench_batch_device.restype = C.c_int
+        lib.a1mpc_balance_solve_batch_device.argtypes = [vp, C.POINTER(BalanceConfig), i32] + [vpp] * 9 + [vpp]; lib.a1mpc_balance_solve_batch_device.restype = C.c_int
+        lib.a1mpc_contacts_batch.argtypes = [vp, C.POINTER(ContactConfig), i32, dp, u8p, dp, dp, u8p, dp]; lib.a1mpc_contacts_batch.restype = C.c_int
+        lib.a1mpc_contacts_batch_device.argtypes = [vp, C.POINTER(ContactConfig), i32] + [vpp] * 6 + [vpp]; lib.a1mpc_contacts_batch_device.restype = C.c_int
+        lib.a1mpc_control_tick_balance_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(BalanceTick), C.POINTER(TickBuffers), i32, vp]
+        lib.a1mpc_control_tick_balance_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_last_tick_stage_cycles"):  # (round 5; an older build bound by hand for an A/B may lack it)
         lib.a1mpc_last_tick_stage_cycles.argtypes = [vp, dp, C.POINTER(C.c_int32)]; lib.a1mpc_last_tick_stage_cycles.restype = C.c_int
     lib.a1mpc_set_schedule.argtypes = [vp, i32]; lib.a1mpc_set_schedule.restype = C.c_int
@@ -504,6 +523,69 @@ class Engine:
                                                 contact.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(grf), _dp(f), _ip(iters), _ip(status))
         _check(self.lib, rc, "a1mpc_balance_solve_batch")
         return dict(grf=grf, f_world=f, iters=iters, status=status)
+
+    # ---- the balance-QP stance controller (stance_leg_control_type 0, S/A1RobotControl.cpp:325-332, 377-444): PD wrench, device solve, contact block, one-call tick ----
+    def balance_gains(self, **fields):
+        """a1mpc_default_balance_gains with `fields` (kp_linear, kd_linear, kp_angular, kd_angular: three numbers each) overridden"""
+        g = BalanceGains(); self.lib.a1mpc_default_balance_gains(C.byref(g))
+        for k, v in fields.items():
+            getattr(g, k)[:] = [float(x) for x in v]
+        return g
+
+    def balance_wrench(self, root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, root_ang_vel, R, gains=None):
+        """root_acc (n, 6) of a1mpc_balance_wrench_batch: host arrays, *_d velocities in the body frame, the others in the world frame; mass is the handle's"""
+        g = self.balance_gains() if gains is None else gains
+        pd = _f64(root_pos_d, (-1, 3)); n = pd.shape[0]
+        arrs = [pd] + [_f64(a, (n, 3)) for a in (root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, root_ang_vel)] + [_f64(R, (n, 9))]
+        acc = np.zeros((n, 6))
+        _check(self.lib, self.lib.a1mpc_balance_wrench_batch(self._h, C.byref(g), n, *[_dp(a) for a in arrs], _dp(acc)), "a1mpc_balance_wrench_batch")
+        return acc
+
+    def balance_wrench_device(self, n, d_root_pos_d, d_root_pos, d_root_lin_vel_d, d_root_lin_vel, d_root_euler_d, d_root_euler, d_root_ang_vel_d, d_root_ang_vel, d_R,
+                              d_root_acc, gains=None, stream=None):
+        """a1mpc_balance_wrench_batch_device: device pointers (torch tensors), asynchronous on `stream`"""
+        g = self.balance_gains() if gains is None else gains
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        rc = self.lib.a1mpc_balance_wrench_batch_device(self._h, C.byref(g), int(n), ptr(d_root_pos_d), ptr(d_root_pos), ptr(d_root_lin_vel_d), ptr(d_root_lin_vel),
+                                                        ptr(d_root_euler_d), ptr(d_root_euler), ptr(d_root_ang_vel_d), ptr(d_root_ang_vel), ptr(d_R), ptr(d_root_acc),
+                                                        C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_balance_wrench_batch_device")
+
+    def balance_solve_device(self, n, d_root_acc, d_R, d_Rz, d_foot, d_contact, d_grf, d_f_world=None, d_iters=None, d_status=None, qp=None, stream=None):
+        """a1mpc_balance_solve_batch_device: balance_solve on device pointers (torch tensors), asynchronous on `stream`"""
+        if qp is None:
+            qp = BalanceConfig(); self.lib.a1mpc_default_balance_config(C.byref(qp))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        rc = self.lib.a1mpc_balance_solve_batch_device(self._h, C.byref(qp), int(n), ptr(d_root_acc), ptr(d_R), ptr(d_Rz), ptr(d_foot), ptr(d_contact), ptr(d_grf),
+                                                       ptr(d_f_world), ptr(d_iters), ptr(d_status), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_balance_solve_batch_device")
+
+    def contacts(self, gait_counter, plan_contacts, foot_force, foot_pos_abs, cfg=None):
+        """a1mpc_contacts_batch: the contact block of contact_terrain alone, on the same state; the terrain-angle filter is left as it is"""
+        if cfg is None:
+            cfg = ContactConfig(); self.lib.a1mpc_default_contact_config(C.byref(cfg))
+        gc = _f64(gait_counter, (-1, 4)); n = gc.shape[0]; pc = np.ascontiguousarray(plan_contacts, dtype=np.uint8).reshape(n, 4)
+        ff = _f64(foot_force, (n, 4)); fp = _f64(foot_pos_abs, (n, 12))
+        ct = np.zeros((n, 4), np.uint8); rec = np.zeros((n, 12))
+        _check(self.lib, self.lib.a1mpc_contacts_batch(self._h, C.byref(cfg), n, _dp(gc), _u8p(pc), _dp(ff), _dp(fp), _u8p(ct), _dp(rec)), "a1mpc_contacts_batch")
+        return dict(contacts=ct, foot_pos_recent_contact=rec)
+
+    def balance_tick(self, d_root_pos_d, d_root_acc=None, d_f_world=None, gains=None, qp=None):
+        """a BalanceTick: default gains / QP constants unless given, device pointers (torch tensors) for root_pos_d (n, 3) and the optional outputs"""
+        bt = BalanceTick()
+        self.lib.a1mpc_default_balance_gains(C.byref(bt.gains)); self.lib.a1mpc_default_balance_config(C.byref(bt.qp))
+        if gains is not None:
+            bt.gains = gains
+        if qp is not None:
+            bt.qp = qp
+        for k, t in (("root_pos_d", d_root_pos_d), ("root_acc", d_root_acc), ("f_world", d_f_world)):
+            setattr(bt, k, None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
+        return bt
+
+    def control_tick_balance_device(self, params, balance, buffers, n, stream=None):
+        """a1mpc_control_tick_balance_device: one whole control tick of n robots on the balance-QP controller (a BalanceTick beside TickParams / TickBuffers)"""
+        _check(self.lib, self.lib.a1mpc_control_tick_balance_device(self._h, C.byref(params), C.byref(balance), C.byref(buffers), int(n),
+                                                                    C.c_void_p(stream) if stream else None), "a1mpc_control_tick_balance_device")
 
     # ---- N2a: gait plan + Raibert foothold (S/A1RobotControl.cpp:148-202) ----
     def update_plan(self, movement_mode, gait_counter, gait_counter_speed, root_lin_vel, Rz, R, root_pos, root_lin_vel_d, gait=None):

@@ -410,6 +410,62 @@ a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* 
 a1mpc_status a1mpc_last_control_tick_ms(a1mpc_handle h, float* ms_out, int32_t* torques_fused_out);
 
 /*
+ * The balance-QP stance controller on the device (stance_leg_control_type 0 of the reference's rosparam sets): what compute_grf runs instead of the convex MPC,
+ * S/A1RobotControl.cpp:325-332, 377-444 -- a PD wrench on the body, then the 12-variable QP of a1mpc_balance_solve_batch.
+ *
+ * a1mpc_balance_wrench_batch(_device): root_acc, the desired wrench (S/A1RobotControl.cpp:379-391) from the euler error with its yaw wrap at +-3.1415926 * 1.5
+ * (:325-332), for n robots.  kp_linear .* (root_pos_d - root_pos) + R (kd_linear .* (root_lin_vel_d - R' root_lin_vel)) on the first three elements (+ mass * 9.8 on
+ * the third, the handle's cfg.mass), kp_angular .* euler_error + kd_angular .* (root_ang_vel_d - R' root_ang_vel) on the last three.
+ *   root_pos_d, root_pos n x 3; root_lin_vel_d n x 3 (body frame), root_lin_vel n x 3 (world); root_euler_d, root_euler n x 3;
+ *   root_ang_vel_d n x 3 (body frame), root_ang_vel n x 3 (world); R_world n x 9 row-major (root_rot_mat)
+ * out: root_acc n x 6, the layout a1mpc_balance_solve_batch takes.  Element-wise, HBM-bound (27 doubles in, 6 out per robot); IEEE add / subtract / multiply in the
+ * reference's order, not contracted: bit-identical to the reference arithmetic.  A null handle, gains or array, a non-finite gain or n < 0 is
+ * A1MPC_ERR_INVALID_ARGUMENT, n > max_batch A1MPC_ERR_BATCH_TOO_LARGE (a1mpc_last_error names the argument), all before any device call; n == 0 launches nothing.
+ * The _device entry takes device pointers and is asynchronous on `hip_stream` (NULL = the handle's stream); the host entry stages through device memory.
+ */
+typedef struct a1mpc_balance_gains { double kp_linear[3], kd_linear[3], kp_angular[3], kd_angular[3]; } a1mpc_balance_gains;
+void a1mpc_default_balance_gains(a1mpc_balance_gains* gains);   /* S/A1CtrlStates.h:117-120: 1000 x3 | 200, 70, 120 | 650, 35, 1 | 4.5, 4.5, 30 */
+a1mpc_status a1mpc_balance_wrench_batch(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* root_pos_d, const double* root_pos,
+                                        const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d, const double* root_euler,
+                                        const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world, double* root_acc_out);
+a1mpc_status a1mpc_balance_wrench_batch_device(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* d_root_pos_d, const double* d_root_pos,
+                                               const double* d_root_lin_vel_d, const double* d_root_lin_vel, const double* d_root_euler_d, const double* d_root_euler,
+                                               const double* d_root_ang_vel_d, const double* d_root_ang_vel, const double* d_R_world, double* d_root_acc_out,
+                                               void* hip_stream);
+/* a1mpc_balance_solve_batch (S/A1RobotControl.cpp:393-444) on device pointers: asynchronous on `hip_stream` (NULL = the handle's stream), no host synchronisation and no
+ * pinned small-batch block; the same validation, the same kernel launch and the same bits as the host entry.  d_f_world_out, d_iters_out, d_status_out may be NULL.
+ * a1mpc_last_kernel_ms and a1mpc_last_nfact report it. */
+a1mpc_status a1mpc_balance_solve_batch_device(a1mpc_handle h, const a1mpc_balance_config* qp, int32_t n, const double* d_root_acc, const double* d_R_world,
+                                              const double* d_R_z, const double* d_foot_abs, const uint8_t* d_contact, double* d_grf_body_out, double* d_f_world_out,
+                                              int32_t* d_iters_out, int32_t* d_status_out, void* hip_stream);
+/* The contact block of generate_swing_legs_ctrl on its own (S/A1RobotControl.cpp:256-282) -- a1mpc_contact_terrain_batch without the terrain fit, which the reference
+ * skips for this controller (:335, "only do terrain adaptation in MPC").  The early-contact flags and the recent-contact filters are the handle's contact state, the
+ * same a1mpc_contact_terrain_batch uses and a1mpc_reset_contact_state clears; the terrain-angle filter, root_euler_d and the terrain outputs are neither read nor
+ * written (cfg->use_terrain_adapt is ignored).  gait_counter n x 4, plan_contacts n x 4, foot_force n x 4, foot_pos_abs n x 12;
+ * out: contacts n x 4, foot_pos_recent_contact n x 12 -- bit for bit what a1mpc_contact_terrain_batch gives. */
+a1mpc_status a1mpc_contacts_batch(a1mpc_handle h, const a1mpc_contact_config* cfg, int32_t n, const double* gait_counter, const uint8_t* plan_contacts,
+                                  const double* foot_force, const double* foot_pos_abs, uint8_t* contacts_out, double* foot_pos_recent_contact_out);
+a1mpc_status a1mpc_contacts_batch_device(a1mpc_handle h, const a1mpc_contact_config* cfg, int32_t n, const double* d_gait_counter, const uint8_t* d_plan_contacts,
+                                         const double* d_foot_force, const double* d_foot_pos_abs, uint8_t* d_contacts_out, double* d_foot_pos_recent_contact_out,
+                                         void* hip_stream);
+/* One control tick of n robots on the balance-QP controller in ONE call: the leg state, EKF, plan and swing-leg stages of a1mpc_control_tick_device, the contact block
+ * alone, then compute_grf's type-0 branch (S/A1RobotControl.cpp:325-332, 377-444) -- the wrench from this tick's root_pos / root_lin_vel, root_euler(_d), the commanded
+ * velocities and R_world, the balance QP on R_world, R_z, foot_pos_abs and contacts -- and compute_joint_torques (:289-319) as a launch of its own
+ * (a1mpc_last_control_tick_ms reports this tick with torques_fused = 0), back to back on `hip_stream`, no host round trip.  Bit-identical to chaining
+ * a1mpc_leg_state_batch_device, a1mpc_ekf_update_batch_device, a1mpc_update_plan_batch_device, a1mpc_swing_legs_batch_device, a1mpc_contacts_batch_device,
+ * a1mpc_balance_wrench_batch_device, a1mpc_balance_solve_batch_device and a1mpc_joint_torques_batch_device.  Of a1mpc_tick_buffers, root_pos_d_z and terrain_angle are
+ * not used and may be NULL, root_euler_d is read and never written; grf / iters / status are the QP's.  The handle's horizon is irrelevant; its OSQP settings are used
+ * with the warm start forced off, as in a1mpc_balance_solve_batch. */
+typedef struct a1mpc_balance_tick {
+    a1mpc_balance_gains gains; a1mpc_balance_config qp;
+    const double* root_pos_d;   /* device, n x 3 */
+    double* root_acc;           /* device, n x 6 out, or NULL: a handle-owned buffer, allocated once */
+    double* f_world;            /* device, n x 12 out, or NULL */
+} a1mpc_balance_tick;
+a1mpc_status a1mpc_control_tick_balance_device(a1mpc_handle h, const a1mpc_tick_params* params, const a1mpc_balance_tick* balance, const a1mpc_tick_buffers* buffers,
+                                               int32_t n, void* hip_stream);
+
+/*
  * Gait-aware horizon: the device-side PRODUCER of the two inputs a1mpc_solve_batch_strided takes beyond the reference controller's -- a contact schedule over the
  * horizon and per-step feet -- from the state a control tick already holds on the device (gait counters, contacts, feet, the velocity command).
  * NOT the reference controller's behaviour unless switched off: calculate_qp_mats broadcasts the current contacts[] over all H steps (S/ConvexMpc.cpp:228-245) and
