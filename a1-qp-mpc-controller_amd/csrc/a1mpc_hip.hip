@@ -379,39 +379,60 @@ struct WrenchArgs {
     const double *pos_d, *pos, *lin_vel_d, *lin_vel, *euler_d, *euler, *ang_vel_d, *ang_vel, *R;   // n x 3 each, R n x 9 row-major; *_d velocities in the body frame
     double* root_acc;                                                                              // n x 6
 };
-__global__ __launch_bounds__(256) void a1mpc_balance_wrench_kernel(const WrenchArgs a) {
-#pragma clang fp contract(off)
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (b >= a.n) return;
-    double pd[3], p[3], vd[3], v[3], ed[3], e[3], wd[3], w[3], R[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        pd[i] = a.pos_d[b * 3 + i]; p[i] = a.pos[b * 3 + i]; vd[i] = a.lin_vel_d[b * 3 + i]; v[i] = a.lin_vel[b * 3 + i];
-        ed[i] = a.euler_d[b * 3 + i]; e[i] = a.euler[b * 3 + i]; wd[i] = a.ang_vel_d[b * 3 + i]; w[i] = a.ang_vel[b * 3 + i];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = a.R[b * 9 + k];
-    double ee[3], t2[3], acc[6];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ee[i] = ed[i] - e[i];
-    if (ee[2] > 3.1415926 * 1.5) ee[2] = ed[2] - 3.1415926 * 2 - e[2];                              // :328-332 (strict comparisons: a yaw error ON the mark is kept)
-    else if (ee[2] < -3.1415926 * 1.5) ee[2] = ed[2] + 3.1415926 * 2 - e[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double t = vd[i] - (R[0 * 3 + i] * v[0] + R[1 * 3 + i] * v[1] + R[2 * 3 + i] * v[2]);   // root_lin_vel_d - R' root_lin_vel
-        t2[i] = a.kd_lin[i] * t;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        acc[i] = a.kp_lin[i] * (pd[i] - p[i]);                                                       // :380
-        acc[i] = acc[i] + (R[i * 3 + 0] * t2[0] + R[i * 3 + 1] * t2[1] + R[i * 3 + 2] * t2[2]);       // :382-383
-        acc[3 + i] = a.kp_ang[i] * ee[i];                                                            // :385
-        acc[3 + i] = acc[3 + i] + a.kd_ang[i] * (wd[i] - (R[0 * 3 + i] * w[0] + R[1 * 3 + i] * w[1] + R[2 * 3 + i] * w[2]));   // :386-387
-    }
-    acc[2] = acc[2] + a.mass * 9.8;                                                                  // :391
-#pragma unroll
+// a1mpc_balance_wrench_kp_batch: kp_linear[0:2] of every robot from kp_xy (n x 2, what the command stage switches between 0 and the lock values, S/GazeboA1ROS.cpp:172-186)
+// instead of the gains' -- a kernel of its own around the same per-robot body.  The body is a macro, not an inlined function: expanded with the gains' kp_linear it is token
+// for token the kernel this file had before the second one existed, and the compiler gives that kernel the code it gave it then (as an inlined template it did not:
+// the same operations, scheduled otherwise).  LOAD_KP: the statement that loads the per-robot gains with the other inputs; KP_LIN(i): kp_linear[i] of robot b.
+struct WrenchKpArgs { WrenchArgs w; const double* kp_xy; };
+#define A1_WRENCH_ROBOT(LOAD_KP, KP_LIN)                                                                                                                                  \
+    _Pragma("clang fp contract(off)")                                                                                                                                     \
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;                                                                                               \
+    if (b >= a.n) return;                                                                                                                                                 \
+    double pd[3], p[3], vd[3], v[3], ed[3], e[3], wd[3], w[3], R[9];                                                                                                      \
+    LOAD_KP                                                                                                                                                               \
+    _Pragma("unroll")                                                                                                                                                     \
+    for (int i = 0; i < 3; ++i) {                                                                                                                                         \
+        pd[i] = a.pos_d[b * 3 + i]; p[i] = a.pos[b * 3 + i]; vd[i] = a.lin_vel_d[b * 3 + i]; v[i] = a.lin_vel[b * 3 + i];                                                 \
+        ed[i] = a.euler_d[b * 3 + i]; e[i] = a.euler[b * 3 + i]; wd[i] = a.ang_vel_d[b * 3 + i]; w[i] = a.ang_vel[b * 3 + i];                                             \
+    }                                                                                                                                                                     \
+    _Pragma("unroll")                                                                                                                                                     \
+    for (int k = 0; k < 9; ++k) R[k] = a.R[b * 9 + k];                                                                                                                    \
+    double ee[3], t2[3], acc[6];                                                                                                                                          \
+    _Pragma("unroll")                                                                                                                                                     \
+    for (int i = 0; i < 3; ++i) ee[i] = ed[i] - e[i];                                                                                                                     \
+    if (ee[2] > 3.1415926 * 1.5) ee[2] = ed[2] - 3.1415926 * 2 - e[2];                              /* :328-332 (strict comparisons: a yaw error ON the mark is kept) */  \
+    else if (ee[2] < -3.1415926 * 1.5) ee[2] = ed[2] + 3.1415926 * 2 - e[2];                                                                                              \
+    _Pragma("unroll")                                                                                                                                                     \
+    for (int i = 0; i < 3; ++i) {                                                                                                                                         \
+        const double t = vd[i] - (R[0 * 3 + i] * v[0] + R[1 * 3 + i] * v[1] + R[2 * 3 + i] * v[2]);   /* root_lin_vel_d - R' root_lin_vel */                              \
+        t2[i] = a.kd_lin[i] * t;                                                                                                                                          \
+    }                                                                                                                                                                     \
+    _Pragma("unroll")                                                                                                                                                     \
+    for (int i = 0; i < 3; ++i) {                                                                                                                                         \
+        acc[i] = KP_LIN(i) * (pd[i] - p[i]);                                                         /* :380 */                                                           \
+        acc[i] = acc[i] + (R[i * 3 + 0] * t2[0] + R[i * 3 + 1] * t2[1] + R[i * 3 + 2] * t2[2]);       /* :382-383 */                                                      \
+        acc[3 + i] = a.kp_ang[i] * ee[i];                                                            /* :385 */                                                           \
+        acc[3 + i] = acc[3 + i] + a.kd_ang[i] * (wd[i] - (R[0 * 3 + i] * w[0] + R[1 * 3 + i] * w[1] + R[2 * 3 + i] * w[2]));   /* :386-387 */                             \
+    }                                                                                                                                                                     \
+    acc[2] = acc[2] + a.mass * 9.8;                                                                  /* :391 */                                                           \
+    _Pragma("unroll")                                                                                                                                                     \
     for (int k = 0; k < 6; ++k) a.root_acc[b * 6 + k] = acc[k];
+#define A1_WRENCH_NO_LOAD
+#define A1_WRENCH_GAINS_KP(i) a.kp_lin[i]
+#define A1_WRENCH_LOAD_ROW_KP const double kp_row[3] = {k.kp_xy[b * 2 + 0], k.kp_xy[b * 2 + 1], a.kp_lin[2]};
+#define A1_WRENCH_ROW_KP(i) kp_row[i]
+__global__ __launch_bounds__(256) void a1mpc_balance_wrench_kernel(const WrenchArgs a) {
+    A1_WRENCH_ROBOT(A1_WRENCH_NO_LOAD, A1_WRENCH_GAINS_KP)
 }
+__global__ __launch_bounds__(256) void a1mpc_balance_wrench_kp_kernel(const WrenchKpArgs k) {
+    const WrenchArgs& a = k.w;
+    { A1_WRENCH_ROBOT(A1_WRENCH_LOAD_ROW_KP, A1_WRENCH_ROW_KP) }   // (a block of its own: the contraction pragma must open a compound statement)
+}
+#undef A1_WRENCH_ROBOT
+#undef A1_WRENCH_NO_LOAD
+#undef A1_WRENCH_GAINS_KP
+#undef A1_WRENCH_LOAD_ROW_KP
+#undef A1_WRENCH_ROW_KP
 
 // ---- predicted horizon states and the cost of a force plan (a1mpc_horizon_states_batch): x_(t+1) = A_d x_t + B_d,t u_t rolled out from x0, i.e. A_qp x0 + B_qp u of the
 // reference's public members (S/ConvexMpc.h, S/ConvexMpc.cpp:181-202) without forming either, and the two sums 1/2 e'Qe, 1/2 u'Ru.  Memory-bound: 25H + 34 doubles in,
@@ -845,6 +866,10 @@ struct a1mpc_handle_s {
     double* d_tickrec = nullptr;    // a1mpc_control_tick_device: n x 22 tick records + 3 doubles (km_foot), allocated on first use
     uint32_t* d_pv_sched = nullptr; // a1mpc_control_tick_preview_device: n x H words, the horizon's contact schedule (allocated on first use)
     double* d_pv_foot = nullptr;    // ... and n x 12H per-step feet (allocated on first use)
+    double* d_sensor_filt = nullptr;      // a1mpc_sensor_frontend_batch: the six IMU filters of every robot, [6][window + 2][max_batch] (allocated on first use, for the window in use)
+    int32_t* d_sensor_cursor = nullptr;   // ... and their shared count / cursor, [2][max_batch]
+    int32_t sensor_window = 0;            // the window the state was built with (0: none since the last reset); sensor_alloc_window: what the allocation holds
+    int32_t sensor_alloc_window = 0;
     double* d_bal_acc = nullptr;    // a1mpc_control_tick_balance_device: n x 6 root_acc where the caller passes no buffer of its own (allocated on first use)
     double *d_hs_u = nullptr, *d_hs_x = nullptr;   // a1mpc_horizon_states_batch (host pointers): n x 12H forces in, n x 13H predicted states out (allocated on first use)
     int32_t ekf_ready_n = 0;        // robots 0 .. ekf_ready_n - 1 have had their filter initialised (the init kernel is not launched for them again)
@@ -1178,6 +1203,156 @@ static void launch_contacts(a1mpc_handle h, const a1mpc_contact_config& cfg, int
     hipLaunchKernelGGL(a1mpc_contacts_kernel, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, s, a);
 }
 
+// ---- sensor front end (a1mpc_sensor_frontend_batch): what the reference's callbacks make of a quaternion and a raw IMU sample -- gt_pose_callback
+// (S/GazeboA1ROS.cpp:235-262: root_rot_mat, root_euler, root_rot_mat_z) and imu_callback (:284-300: six MovingWindowFilter(5), root_ang_vel = root_rot_mat * imu_ang_vel).
+// One lane per robot, workgroups of 256; 10 doubles in, 30 out, and the six filters' state.
+//   state     field-major, [filter][slot 0 .. window - 1 | sum | corr][robot] with `stride` robots per field, then [count | head][robot] as int32: a wavefront's access to
+//             one field is one contiguous run of 512 bytes (256 for the two cursors) while the robots' cursors agree, and neighbouring words of `window` runs where they
+//             have parted (a call with fewer robots in between).  The six filters of a robot are always updated together and share one count and one cursor.  The window
+//             is addressed in memory, by the cursor: no per-lane array, nothing for the compiler to put into scratch.
+//   loads     the raw sample, the cursors and the twelve sums / corrections are issued before the first operation, the six slots under the cursor behind the cursor's
+//             arrival (the only dependent load); every store follows the last operation.
+//   bits      contraction off; Eigen's operation order for both matrices (Quaternion::toRotationMatrix; AngleAxis::toRotationMatrix with the axis (0, 0, 1) written out,
+//             products with the axis' zeros included: a NaN yaw fills the matrix as it does there), S/utils/Utils.cpp:7-33 for the angles with the clamp of t2, the
+//             filters as S/utils/filter.hpp:26-62 (Neumaier, the division by the window length from the first sample on): everything but atan2, asin, sin and cos is the
+//             reference's arithmetic bit for bit.  The quaternion is not normalised, as in the reference.
+// Plain C++ without intrinsics: the CPU suite compiles this section for the host (tests/emu/frontend_host.py).
+constexpr int kImuWindowMax = A1MPC_IMU_WINDOW_MAX;
+constexpr int kImuFilters = 6;   // acc x, y, z, gyro x, y, z
+struct SensorArgs {
+    int32_t n, window;
+    int64_t stride;                               // robots per state field (= max_batch)
+    const double *quat, *acc_raw, *gyro_raw;      // n x 4 (w, x, y, z), n x 3, n x 3
+    double* filt;                                 // [6][window + 2][stride]
+    int32_t* cursor;                              // [2][stride]: samples held (<= window), next slot
+    double *R_world, *R_z, *euler, *acc, *gyro, *ang_vel;
+};
+__global__ __launch_bounds__(256) void a1mpc_sensor_frontend_kernel(const SensorArgs a) {
+#pragma clang fp contract(off)
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= a.n) return;
+    const int64_t fields = a.window + 2;
+    const double qw = a.quat[b * 4 + 0], x = a.quat[b * 4 + 1], y = a.quat[b * 4 + 2], z = a.quat[b * 4 + 3];
+    double raw[kImuFilters];
+    Neumaier f[kImuFilters];
+    const int32_t count = a.cursor[b], head = a.cursor[a.stride + b];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { raw[i] = a.acc_raw[b * 3 + i]; raw[3 + i] = a.gyro_raw[b * 3 + i]; }
+#pragma unroll
+    for (int k = 0; k < kImuFilters; ++k) {
+        const double* fk = a.filt + (k * fields + a.window) * a.stride + b;
+        f[k].sum = fk[0]; f[k].corr = fk[a.stride];
+    }
+    double old[kImuFilters];
+#pragma unroll
+    for (int k = 0; k < kImuFilters; ++k) old[k] = a.filt[(k * fields + head) * a.stride + b];
+    // Eigen::Quaternion::toRotationMatrix
+    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+    const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    double R[9];
+    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+    // Utils::quat_to_euler, S/utils/Utils.cpp:17-31
+    const double y_sqr = y * y;
+    const double t0 = 2.0 * (qw * x + y * z), t1 = 1.0 - 2.0 * (x * x + y_sqr);
+    double t2 = 2.0 * (qw * y - z * x);
+    t2 = t2 > 1.0 ? 1.0 : t2;
+    t2 = t2 < -1.0 ? -1.0 : t2;
+    const double t3 = 2.0 * (qw * z + x * y), t4 = 1.0 - 2.0 * (y_sqr + z * z);
+    const double roll = atan2(t0, t1), pitch = asin(t2), yaw = atan2(t3, t4);
+    // Eigen::AngleAxisd(yaw, UnitZ()).toRotationMatrix(): sin_axis = s * axis, cos1_axis = (1 - c) * axis, the off-diagonal pairs tmp -+ sin_axis, the diagonal cos1_axis .* axis + c
+    const double sn = sin(yaw), c = cos(yaw);
+    const double ax = 0.0, ay = 0.0, az = 1.0;
+    const double sx = sn * ax, sy = sn * ay, sz = sn * az, cx = (1.0 - c) * ax, cy = (1.0 - c) * ay, cz = (1.0 - c) * az;
+    double Rz[9];
+    double tmp = cx * ay; Rz[1] = tmp - sz; Rz[3] = tmp + sz;
+    tmp = cx * az; Rz[2] = tmp + sy; Rz[6] = tmp - sy;
+    tmp = cy * az; Rz[5] = tmp - sx; Rz[7] = tmp + sx;
+    Rz[0] = cx * ax + c; Rz[4] = cy * ay + c; Rz[8] = cz * az + c;
+    // MovingWindowFilter::CalculateAverage, S/utils/filter.hpp:26-39
+    const bool full = count >= a.window;
+    const double wlen = static_cast<double>(a.window);
+    double avg[kImuFilters];
+#pragma unroll
+    for (int k = 0; k < kImuFilters; ++k) {
+        if (full) f[k].add(-old[k]);
+        f[k].add(raw[k]);
+        avg[k] = (f[k].sum + f[k].corr) / wlen;
+    }
+    double wv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) wv[i] = R[i * 3 + 0] * avg[3] + R[i * 3 + 1] * avg[4] + R[i * 3 + 2] * avg[5];   // :299
+#pragma unroll
+    for (int k = 0; k < kImuFilters; ++k) {
+        double* fk = a.filt + (k * fields + a.window) * a.stride + b;
+        a.filt[(k * fields + head) * a.stride + b] = raw[k];
+        fk[0] = f[k].sum; fk[a.stride] = f[k].corr;
+    }
+    a.cursor[b] = full ? count : count + 1;
+    a.cursor[a.stride + b] = head + 1 == a.window ? 0 : head + 1;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { a.R_world[b * 9 + k] = R[k]; a.R_z[b * 9 + k] = Rz[k]; }
+    a.euler[b * 3 + 0] = roll; a.euler[b * 3 + 1] = pitch; a.euler[b * 3 + 2] = yaw;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { a.acc[b * 3 + i] = avg[i]; a.gyro[b * 3 + i] = avg[3 + i]; a.ang_vel[b * 3 + i] = wv[i]; }
+}
+
+// ---- command stage (a1mpc_command_batch): the first half of main_update, S/GazeboA1ROS.cpp:124-188, branch for branch -- body-height integrator with its clamps, the mode
+// toggle, the commanded velocities, root_euler_d's integration, the xy position lock and the switching of kp_linear[0:2] -- and the mpc_init_counter gate of
+// compute_joint_torques (S/A1RobotControl.cpp:292-294).  One lane per robot, workgroups of 256, element-wise: every load before the first operation, every store behind the
+// last.  Contraction off (cmd * dt is rounded before it is added); sqrt is IEEE's.  Plain C++ without intrinsics (tests/emu/frontend_host.py compiles this section too).
+struct CommandArgs {
+    int32_t n, init_ticks;
+    double dt, height_max, height_min, lock_x, lock_y, lock_speed;
+    const double *cmd, *root_pos;    // n x 6 (velx, vely, velz, roll / pitch / yaw rate), n x 3
+    const uint8_t* toggle;           // n
+    double *body_height, *euler_d, *pos_d, *kp_xy;   // in/out: n, n x 3, n x 3, n x 2
+    uint8_t* ctrl_state;             // in/out, n
+    int32_t* init_counter;           // in/out, n
+    double *lin_vel_d, *ang_vel_d, *pos_d_z;         // out: n x 3, n x 3, n
+    uint8_t *movement_mode, *mpc_active;             // out: n
+};
+__global__ __launch_bounds__(256) void a1mpc_command_kernel(const CommandArgs a) {
+#pragma clang fp contract(off)
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= a.n) return;
+    double cmd[6], ed[3], pd[2], kp[2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cmd[k] = a.cmd[b * 6 + k];
+    const double px = a.root_pos[b * 3 + 0], py = a.root_pos[b * 3 + 1];
+    double height = a.body_height[b];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ed[i] = a.euler_d[b * 3 + i];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { pd[i] = a.pos_d[b * 3 + i]; kp[i] = a.kp_xy[b * 2 + i]; }
+    const int prev = a.ctrl_state[b];
+    const bool toggle = a.toggle[b] != 0;
+    int32_t ticks = a.init_counter[b];
+    height = height + cmd[2] * a.dt;                                            // :124-130
+    if (height >= a.height_max) height = a.height_max;
+    if (height <= a.height_min) height = a.height_min;
+    int state = prev;
+    if (toggle) state = (state + 1) % 2;                                        // :142-147
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ed[i] = ed[i] + cmd[3 + i] * a.dt;              // :158-160
+    int mode;
+    if (state == 1) mode = 1;                                                   // :164-176
+    else if (state == 0 && prev == 1) { mode = 0; pd[0] = px; pd[1] = py; kp[0] = a.lock_x; kp[1] = a.lock_y; }   // leave walking mode: one tick only
+    else mode = 0;
+    if (mode == 1) {                                                            // :179-188
+        if (sqrt(cmd[0] * cmd[0] + cmd[1] * cmd[1]) > a.lock_speed) { pd[0] = px; pd[1] = py; kp[0] = 0.0; kp[1] = 0.0; }
+        else { kp[0] = a.lock_x; kp[1] = a.lock_y; }
+    }
+    if (ticks < 2147483647) ticks = ticks + 1;                                  // S/A1RobotControl.cpp:292 (an int there too; held at its maximum here)
+    a.body_height[b] = height; a.ctrl_state[b] = static_cast<uint8_t>(state); a.init_counter[b] = ticks;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { a.euler_d[b * 3 + i] = ed[i]; a.lin_vel_d[b * 3 + i] = cmd[i]; a.ang_vel_d[b * 3 + i] = cmd[3 + i]; }
+    a.pos_d[b * 3 + 0] = pd[0]; a.pos_d[b * 3 + 1] = pd[1]; a.pos_d[b * 3 + 2] = height; a.pos_d_z[b] = height;
+    a.kp_xy[b * 2 + 0] = kp[0]; a.kp_xy[b * 2 + 1] = kp[1];
+    a.movement_mode[b] = static_cast<uint8_t>(mode); a.mpc_active[b] = ticks >= a.init_ticks ? 1 : 0;
+}
+
 // ---- what the entry points of the caller-side stages share.  A stage has a launcher (launch_<stage>: scalars and DEVICE pointers in, the args struct filled and the
 // kernel launched on a stream the caller has ordered) and two entries around it: the device-pointer one is the macros below and the launcher, the host-pointer
 // one also stages the caller's arrays through the handle's staging buffers (Staging) on the handle's stream.
@@ -1206,7 +1381,7 @@ static hipStream_t stream_or_own(a1mpc_handle h, void* hip_stream) { return hip_
 
 // The handle's staging for the host-pointer entries, allocated on first use.  Per robot: kAuxIn + kAuxOut doubles in two blocks, and kAuxU8 bytes handed out in
 // slices of kAuxU8Slice (every byte array starts 8-byte aligned whatever the batch size)
-constexpr size_t kAuxIn = 64, kAuxOut = 96, kAuxU8 = 16, kAuxU8Slice = 8;
+constexpr size_t kAuxIn = 64, kAuxOut = 96, kAuxU8 = 32, kAuxU8Slice = 8;   // (four byte arrays: a1mpc_command_batch)
 static a1mpc_status ensure_aux(a1mpc_handle h) {
     if (h->d_aux_in) return A1MPC_OK;
     const size_t n = static_cast<size_t>(h->max_batch);
@@ -1224,7 +1399,7 @@ struct Staging {
     a1mpc_handle h; size_t N; hipStream_t s;
     a1mpc_status st;
     size_t used_in = 0, used_out = 0, used_u8 = 0;   // per robot
-    Back backs[8]; int n_backs = 0;
+    Back backs[12]; int n_backs = 0;   // (a1mpc_command_batch: six in/out arrays and five outputs)
     Staging(a1mpc_handle h_, int32_t n, hipStream_t s_) : h(h_), N(static_cast<size_t>(n)), s(s_), st(ensure_aux(h_)) {}
     void hip(hipError_t e, const char* what) { if (e != hipSuccess) st = fail(A1MPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
     void refuse(const char* what) { st = fail(A1MPC_ERR_INVALID_ARGUMENT, std::string("internal: ") + what + " beyond what the handle's staging holds"); }
@@ -2069,6 +2244,218 @@ a1mpc_status a1mpc_balance_wrench_batch_device(a1mpc_handle h, const a1mpc_balan
 }
 #undef A1_WRENCH_BEGIN
 
+// a1mpc_balance_wrench_batch with kp_linear[0:2] per robot (kp_linear_xy, n x 2): what the command stage switches (a1mpc_command_batch)
+static void launch_wrench_kp(a1mpc_handle h, const a1mpc_balance_gains& g, int32_t n, const double* kp_linear_xy, const double* root_pos_d, const double* root_pos,
+                             const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d, const double* root_euler, const double* root_ang_vel_d,
+                             const double* root_ang_vel, const double* R_world, double* root_acc, hipStream_t s) {
+    WrenchKpArgs k;
+    WrenchArgs& a = k.w;
+    a.n = n; a.mass = h->cfg.mass;
+    for (int i = 0; i < 3; ++i) { a.kp_lin[i] = g.kp_linear[i]; a.kd_lin[i] = g.kd_linear[i]; a.kp_ang[i] = g.kp_angular[i]; a.kd_ang[i] = g.kd_angular[i]; }
+    a.pos_d = root_pos_d; a.pos = root_pos; a.lin_vel_d = root_lin_vel_d; a.lin_vel = root_lin_vel; a.euler_d = root_euler_d; a.euler = root_euler;
+    a.ang_vel_d = root_ang_vel_d; a.ang_vel = root_ang_vel; a.R = R_world; a.root_acc = root_acc;
+    k.kp_xy = kp_linear_xy;
+    hipLaunchKernelGGL(a1mpc_balance_wrench_kp_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 255) / 256)), dim3(256), 0, s, k);
+}
+#define A1_WRENCH_KP_BEGIN(hip_stream)                                                                                                  \
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");                                                                      \
+    if (const char* bad = invalid_balance_gains(gains)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);                                    \
+    if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");                                                                    \
+    if (!kp_linear_xy) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null kp_linear_xy");                                                     \
+    if (const char* bad = null_wrench_array(root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, \
+                                            root_ang_vel, R_world, root_acc_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);          \
+    A1_STAGE_DEVICE(hip_stream)
+a1mpc_status a1mpc_balance_wrench_kp_batch(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* kp_linear_xy, const double* root_pos_d,
+                                           const double* root_pos, const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d,
+                                           const double* root_euler, const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world, double* root_acc_out) {
+    A1_WRENCH_KP_BEGIN(nullptr);
+    Staging sg(h, n, s);
+    const double *d_kp = sg.in(kp_linear_xy, 2), *d_pd = sg.in(root_pos_d, 3), *d_p = sg.in(root_pos, 3), *d_vd = sg.in(root_lin_vel_d, 3), *d_v = sg.in(root_lin_vel, 3),
+                 *d_ed = sg.in(root_euler_d, 3), *d_e = sg.in(root_euler, 3), *d_wd = sg.in(root_ang_vel_d, 3), *d_w = sg.in(root_ang_vel, 3), *d_R = sg.in(R_world, 9);
+    double* d_acc = sg.out(root_acc_out, 6);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_wrench_kp(h, *gains, n, d_kp, d_pd, d_p, d_vd, d_v, d_ed, d_e, d_wd, d_w, d_R, d_acc, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_balance_wrench_kp_batch_device(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* kp_linear_xy, const double* root_pos_d,
+                                                  const double* root_pos, const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d,
+                                                  const double* root_euler, const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world,
+                                                  double* root_acc_out, void* hip_stream) {
+    A1_WRENCH_KP_BEGIN(hip_stream);
+    A1_STAGE_LAUNCH(launch_wrench_kp(h, *gains, n, kp_linear_xy, root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, root_ang_vel,
+                                     R_world, root_acc_out, s));
+    return A1MPC_OK;
+}
+#undef A1_WRENCH_KP_BEGIN
+
+// ---- the sensor and command front end (a1mpc_sensor_frontend_batch, a1mpc_command_batch): entries around a1mpc_sensor_frontend_kernel / a1mpc_command_kernel
+void a1mpc_default_sensor_config(a1mpc_sensor_config* c) {
+    if (!c) return;
+    c->imu_window = 5;   // S/GazeboA1ROS.cpp:99-104: MovingWindowFilter(5), six of them
+}
+void a1mpc_default_command_config(a1mpc_command_config* c) {
+    if (!c) return;
+    c->body_height_max = 0.32; c->body_height_min = 0.1;   // JOY_CMD_BODY_HEIGHT_MAX / _MIN, S/A1Params.h:16-17
+    c->kp_linear_lock_x = 120.0; c->kp_linear_lock_y = 120.0;   // a1_kp_linear_x / _y, S/A1CtrlStates.h:273-274, 298-299
+    c->lock_speed = 0.05;                                  // S/GazeboA1ROS.cpp:180
+    c->mpc_init_ticks = 10;                                // S/A1RobotControl.cpp:294
+}
+static const char* invalid_sensor_config(const a1mpc_sensor_config* c) {
+    if (!c) return "null a1mpc_sensor_config";
+    if (c->imu_window < 1 || c->imu_window > kImuWindowMax) return "a1mpc_sensor_config.imu_window outside 1 .. 64";
+    return nullptr;
+}
+static const char* invalid_command_config(const a1mpc_command_config* c) {
+    if (!c) return "null a1mpc_command_config";
+    const double v[5] = {c->body_height_max, c->body_height_min, c->kp_linear_lock_x, c->kp_linear_lock_y, c->lock_speed};
+    if (!all_finite(v, 5)) return "non-finite value in a1mpc_command_config";
+    if (c->body_height_min > c->body_height_max) return "a1mpc_command_config.body_height_min > body_height_max";
+    return nullptr;
+}
+struct SensorIo { const double *quat, *imu_acc_raw, *imu_gyro_raw; double *R_world, *R_z, *root_euler, *imu_acc, *imu_ang_vel, *root_ang_vel; };
+struct CommandIo {
+    const double* cmd; const uint8_t* mode_toggle; const double* root_pos; double dt;
+    double* body_height; uint8_t* ctrl_state; double *root_euler_d, *root_pos_d, *kp_linear_xy; int32_t* mpc_init_counter;
+    double *root_lin_vel_d, *root_ang_vel_d; uint8_t *movement_mode, *mpc_active; double* root_pos_d_z;
+};
+static const char* null_sensor_array(const SensorIo& io) {
+    const struct { const void* p; const char* what; } arrays[] = {{io.quat, "null quat"}, {io.imu_acc_raw, "null imu_acc_raw"}, {io.imu_gyro_raw, "null imu_gyro_raw"},
+        {io.R_world, "null R_world"}, {io.R_z, "null R_z"}, {io.root_euler, "null root_euler"}, {io.imu_acc, "null imu_acc"}, {io.imu_ang_vel, "null imu_ang_vel"},
+        {io.root_ang_vel, "null root_ang_vel"}};
+    for (const auto& q : arrays) if (!q.p) return q.what;
+    return nullptr;
+}
+static const char* null_command_array(const CommandIo& io) {
+    const struct { const void* p; const char* what; } arrays[] = {{io.cmd, "null cmd"}, {io.mode_toggle, "null mode_toggle"}, {io.root_pos, "null root_pos"},
+        {io.body_height, "null body_height"}, {io.ctrl_state, "null ctrl_state"}, {io.root_euler_d, "null root_euler_d"}, {io.root_pos_d, "null root_pos_d"},
+        {io.kp_linear_xy, "null kp_linear_xy"}, {io.mpc_init_counter, "null mpc_init_counter"}, {io.root_lin_vel_d, "null root_lin_vel_d"},
+        {io.root_ang_vel_d, "null root_ang_vel_d"}, {io.movement_mode, "null movement_mode"}, {io.mpc_active, "null mpc_active"}, {io.root_pos_d_z, "null root_pos_d_z"}};
+    for (const auto& q : arrays) if (!q.p) return q.what;
+    return nullptr;
+}
+// every refusal of the two stages that needs no device: the message, or null
+static const char* invalid_sensor_call(a1mpc_handle h, const a1mpc_sensor_config* cfg, int32_t n, const SensorIo& io) {
+    if (const char* bad = invalid_sensor_config(cfg)) return bad;
+    if (n < 0) return "negative n";
+    if (const char* bad = null_sensor_array(io)) return bad;
+    if (h->sensor_window != 0 && h->sensor_window != cfg->imu_window) return "a1mpc_sensor_config.imu_window differs from the window the filter state was built with (a1mpc_reset_sensor_state first)";
+    return nullptr;
+}
+static const char* invalid_command_call(const a1mpc_command_config* cfg, int32_t n, const CommandIo& io) {
+    if (const char* bad = invalid_command_config(cfg)) return bad;
+    if (n < 0) return "negative n";
+    if (!std::isfinite(io.dt)) return "non-finite dt";
+    return null_command_array(io);
+}
+// the handle's IMU filter state for `window`: [6][window + 2][max_batch] doubles and [2][max_batch] cursors, zero = every filter empty.  A larger window than the
+// allocation holds can only arrive after a reset (invalid_sensor_call), which has waited for the previous launches: the old block is free to go
+static a1mpc_status ensure_sensor_state(a1mpc_handle h, int32_t window, hipStream_t s) {
+    const size_t N = static_cast<size_t>(h->max_batch);
+    if (h->d_sensor_filt && h->sensor_alloc_window < window) { A1_HIP(hipFree(h->d_sensor_filt)); h->d_sensor_filt = nullptr; }
+    const bool fresh = !h->d_sensor_filt || !h->d_sensor_cursor;
+    if (!h->d_sensor_filt) {
+        A1_HIP(hipMalloc(&h->d_sensor_filt, N * kImuFilters * (static_cast<size_t>(window) + 2) * sizeof(double)));
+        h->sensor_alloc_window = window;
+    }
+    if (!h->d_sensor_cursor) A1_HIP(hipMalloc(&h->d_sensor_cursor, N * 2 * sizeof(int32_t)));
+    if (fresh) {
+        A1_HIP(hipMemsetAsync(h->d_sensor_filt, 0, N * kImuFilters * (static_cast<size_t>(h->sensor_alloc_window) + 2) * sizeof(double), s));
+        A1_HIP(hipMemsetAsync(h->d_sensor_cursor, 0, N * 2 * sizeof(int32_t), s));
+    }
+    h->sensor_window = window;
+    return A1MPC_OK;
+}
+static void launch_sensor(a1mpc_handle h, int32_t window, int32_t n, const SensorIo& io, hipStream_t s) {
+    SensorArgs a;
+    a.n = n; a.window = window; a.stride = h->max_batch;
+    a.quat = io.quat; a.acc_raw = io.imu_acc_raw; a.gyro_raw = io.imu_gyro_raw; a.filt = h->d_sensor_filt; a.cursor = h->d_sensor_cursor;
+    a.R_world = io.R_world; a.R_z = io.R_z; a.euler = io.root_euler; a.acc = io.imu_acc; a.gyro = io.imu_ang_vel; a.ang_vel = io.root_ang_vel;
+    hipLaunchKernelGGL(a1mpc_sensor_frontend_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 255) / 256)), dim3(256), 0, s, a);
+}
+static void launch_command(const a1mpc_command_config& c, int32_t n, const CommandIo& io, hipStream_t s) {
+    CommandArgs a;
+    a.n = n; a.init_ticks = c.mpc_init_ticks; a.dt = io.dt; a.height_max = c.body_height_max; a.height_min = c.body_height_min;
+    a.lock_x = c.kp_linear_lock_x; a.lock_y = c.kp_linear_lock_y; a.lock_speed = c.lock_speed;
+    a.cmd = io.cmd; a.root_pos = io.root_pos; a.toggle = io.mode_toggle; a.body_height = io.body_height; a.euler_d = io.root_euler_d; a.pos_d = io.root_pos_d;
+    a.kp_xy = io.kp_linear_xy; a.ctrl_state = io.ctrl_state; a.init_counter = io.mpc_init_counter; a.lin_vel_d = io.root_lin_vel_d; a.ang_vel_d = io.root_ang_vel_d;
+    a.pos_d_z = io.root_pos_d_z; a.movement_mode = io.movement_mode; a.mpc_active = io.mpc_active;
+    hipLaunchKernelGGL(a1mpc_command_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 255) / 256)), dim3(256), 0, s, a);
+}
+a1mpc_status a1mpc_reset_sensor_state(a1mpc_handle h) {
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
+    h->sensor_window = 0;
+    if (!h->d_sensor_filt || !h->d_sensor_cursor) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    A1_ORDER(h, h->stream);  // the memsets below must not overtake a launch still running on a caller's stream
+    A1_HIP(hipMemsetAsync(h->d_sensor_filt, 0, static_cast<size_t>(h->max_batch) * kImuFilters * (static_cast<size_t>(h->sensor_alloc_window) + 2) * sizeof(double), h->stream));
+    A1_HIP(hipMemsetAsync(h->d_sensor_cursor, 0, static_cast<size_t>(h->max_batch) * 2 * sizeof(int32_t), h->stream));
+    A1_HIP(hipStreamSynchronize(h->stream));
+    return A1MPC_OK;
+}
+#define A1_SENSOR_BEGIN(hip_stream)                                                                                      \
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");                                                       \
+    const SensorIo io{quat, imu_acc_raw, imu_gyro_raw, R_world_out, R_z_out, root_euler_out, imu_acc_out, imu_ang_vel_out, root_ang_vel_out}; \
+    if (const char* bad = invalid_sensor_call(h, cfg, n, io)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);               \
+    A1_STAGE_DEVICE(hip_stream)
+a1mpc_status a1mpc_sensor_frontend_batch(a1mpc_handle h, const a1mpc_sensor_config* cfg, int32_t n, const double* quat, const double* imu_acc_raw, const double* imu_gyro_raw,
+                                         double* R_world_out, double* R_z_out, double* root_euler_out, double* imu_acc_out, double* imu_ang_vel_out, double* root_ang_vel_out) {
+    A1_SENSOR_BEGIN(nullptr);
+    Staging sg(h, n, s);
+    if (a1mpc_status st = ensure_sensor_state(h, cfg->imu_window, s); st != A1MPC_OK) return st;
+    SensorIo d;
+    d.quat = sg.in(quat, 4); d.imu_acc_raw = sg.in(imu_acc_raw, 3); d.imu_gyro_raw = sg.in(imu_gyro_raw, 3);
+    d.R_world = sg.out(R_world_out, 9); d.R_z = sg.out(R_z_out, 9); d.root_euler = sg.out(root_euler_out, 3); d.imu_acc = sg.out(imu_acc_out, 3);
+    d.imu_ang_vel = sg.out(imu_ang_vel_out, 3); d.root_ang_vel = sg.out(root_ang_vel_out, 3);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_sensor(h, cfg->imu_window, n, d, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_sensor_frontend_batch_device(a1mpc_handle h, const a1mpc_sensor_config* cfg, int32_t n, const double* quat, const double* imu_acc_raw,
+                                                const double* imu_gyro_raw, double* R_world_out, double* R_z_out, double* root_euler_out, double* imu_acc_out,
+                                                double* imu_ang_vel_out, double* root_ang_vel_out, void* hip_stream) {
+    A1_SENSOR_BEGIN(hip_stream);
+    if (a1mpc_status st = ensure_sensor_state(h, cfg->imu_window, s); st != A1MPC_OK) return st;
+    A1_STAGE_LAUNCH(launch_sensor(h, cfg->imu_window, n, io, s));
+    return A1MPC_OK;
+}
+#undef A1_SENSOR_BEGIN
+#define A1_COMMAND_BEGIN(hip_stream)                                                                                      \
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");                                                       \
+    const CommandIo io{cmd, mode_toggle, root_pos, dt, body_height, ctrl_state, root_euler_d, root_pos_d, kp_linear_xy, mpc_init_counter, root_lin_vel_d_out, \
+                       root_ang_vel_d_out, movement_mode_out, mpc_active_out, root_pos_d_z_out};                           \
+    if (const char* bad = invalid_command_call(cfg, n, io)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);                 \
+    A1_STAGE_DEVICE(hip_stream)
+a1mpc_status a1mpc_command_batch(a1mpc_handle h, const a1mpc_command_config* cfg, int32_t n, const double* cmd, const uint8_t* mode_toggle, const double* root_pos, double dt,
+                                 double* body_height, uint8_t* ctrl_state, double* root_euler_d, double* root_pos_d, double* kp_linear_xy, int32_t* mpc_init_counter,
+                                 double* root_lin_vel_d_out, double* root_ang_vel_d_out, uint8_t* movement_mode_out, uint8_t* mpc_active_out, double* root_pos_d_z_out) {
+    A1_COMMAND_BEGIN(nullptr);
+    Staging sg(h, n, s);
+    CommandIo d;
+    d.dt = dt;
+    d.cmd = sg.in(cmd, 6); d.mode_toggle = sg.in(mode_toggle, 1); d.root_pos = sg.in(root_pos, 3);
+    d.body_height = sg.inout(body_height, 1); d.ctrl_state = sg.inout(ctrl_state, 1); d.root_euler_d = sg.inout(root_euler_d, 3); d.root_pos_d = sg.inout(root_pos_d, 3);
+    d.kp_linear_xy = sg.inout(kp_linear_xy, 2);
+    d.mpc_init_counter = reinterpret_cast<int32_t*>(sg.slice<double>(1));   // (n int32 in a slice of n doubles)
+    if (d.mpc_init_counter) {
+        sg.hip(hipMemcpyAsync(d.mpc_init_counter, mpc_init_counter, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyHostToDevice, s), "hipMemcpyAsync (staging, host to device)");
+        sg.back(mpc_init_counter, static_cast<const int32_t*>(d.mpc_init_counter), 1);
+    }
+    d.root_lin_vel_d = sg.out(root_lin_vel_d_out, 3); d.root_ang_vel_d = sg.out(root_ang_vel_d_out, 3); d.movement_mode = sg.out(movement_mode_out, 1);
+    d.mpc_active = sg.out(mpc_active_out, 1); d.root_pos_d_z = sg.out(root_pos_d_z_out, 1);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_command(*cfg, n, d, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_command_batch_device(a1mpc_handle h, const a1mpc_command_config* cfg, int32_t n, const double* cmd, const uint8_t* mode_toggle, const double* root_pos,
+                                        double dt, double* body_height, uint8_t* ctrl_state, double* root_euler_d, double* root_pos_d, double* kp_linear_xy,
+                                        int32_t* mpc_init_counter, double* root_lin_vel_d_out, double* root_ang_vel_d_out, uint8_t* movement_mode_out, uint8_t* mpc_active_out,
+                                        double* root_pos_d_z_out, void* hip_stream) {
+    A1_COMMAND_BEGIN(hip_stream);
+    A1_STAGE_LAUNCH(launch_command(*cfg, n, io, s));
+    return A1MPC_OK;
+}
+#undef A1_COMMAND_BEGIN
+
 const char* a1mpc_status_string(a1mpc_status s) {
     switch (s) {
         case A1MPC_OK: return "ok";
@@ -2090,7 +2477,7 @@ void a1mpc_destroy(a1mpc_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_tab, h->d_tab1, h->d_x0, h->d_xref, h->d_R, h->d_foot, h->d_aux, h->d_Rz, h->d_contact, h->d_grf,
-                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x, h->d_bal_acc};
+                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x, h->d_bal_acc, h->d_sensor_filt, h->d_sensor_cursor};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -2822,8 +3209,9 @@ void a1mpc_default_tick_params(a1mpc_tick_params* p) {
 // pack and the MPC launch back to back on one stream, no host round trip, and N3 inside the MPC kernel's output stage whenever the tick runs the fused / latency kernel
 // (every warm-started tick of a known batch).  Bit-identical to chaining the seven *_device entry points.
 // pv: the gait-aware horizon (a1mpc_control_tick_preview_device), or null / {0, 0, *}: the plain tick -- the same launches as before the preview existed
-static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream,
-                                      bool footholds = false) {
+// every refusal of a control tick, none of which needs the device: shared by control_tick_impl and by a1mpc_control_tick_sensors_device, which must have made them all
+// before its front end launches
+static a1mpc_status invalid_tick_call(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, bool footholds) {
     if (!h || !p || !bf) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle / params / buffers");
     const bool pv_sched = pv != nullptr && pv->contact_schedule == 1, pv_feet = pv != nullptr && pv->foot_preview != 0;
     if ((pv_sched || pv_feet) && !(p->gait.counter_per_gait > 0)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "a1mpc_gait_config.counter_per_gait <= 0");
@@ -2839,6 +3227,12 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
     if (footholds && pv_feet && !bf->foot_pos_target_abs)
         return fail(A1MPC_ERR_INVALID_ARGUMENT, "null a1mpc_tick_buffers.foot_pos_target_abs: the foothold preview reads it (foot_preview != 0)");
     if (!(p->control_dt > 0)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "control_dt <= 0");
+    return A1MPC_OK;
+}
+static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_preview_config* pv, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream,
+                                      bool footholds = false) {
+    if (a1mpc_status st = invalid_tick_call(h, p, pv, bf, n, footholds); st != A1MPC_OK) return st;
+    const bool pv_sched = pv != nullptr && pv->contact_schedule == 1, pv_feet = pv != nullptr && pv->foot_preview != 0;
     if (n == 0) return A1MPC_OK;
     A1_HIP(hipSetDevice(h->device));
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
@@ -2908,6 +3302,30 @@ static a1mpc_status control_tick_impl(a1mpc_handle h, const a1mpc_tick_params* p
 }
 #undef A1_LAUNCH_EKF
 a1mpc_status a1mpc_control_tick_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
+    return control_tick_impl(h, p, nullptr, bf, n, hip_stream);
+}
+// The control tick from raw inputs: the sensor stage, the command stage, then exactly a1mpc_control_tick_device, back to back on one stream.  Every refusal of the three
+// is made before the first launch (the tick's own by invalid_tick_call, the function control_tick_impl makes them with)
+a1mpc_status a1mpc_control_tick_sensors_device(a1mpc_handle h, const a1mpc_tick_params* p, const a1mpc_tick_sensors* sn, const a1mpc_tick_buffers* bf, int32_t n, void* hip_stream) {
+    if (!h || !p || !sn || !bf) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle / params / sensors / buffers");
+    // the eleven fields the front end produces are inputs of the tick: the caller's storage, written here (a1mpc_tick_buffers declares them const for the tick's sake)
+    const SensorIo si{sn->quat, sn->imu_acc_raw, sn->imu_gyro_raw, const_cast<double*>(bf->R_world), const_cast<double*>(bf->R_z), const_cast<double*>(bf->root_euler),
+                      const_cast<double*>(bf->imu_acc), const_cast<double*>(bf->imu_ang_vel), const_cast<double*>(bf->root_ang_vel)};
+    const CommandIo ci{sn->cmd, sn->mode_toggle, bf->root_pos, p->control_dt, sn->body_height, sn->ctrl_state, bf->root_euler_d, sn->root_pos_d, sn->kp_linear_xy,
+                       sn->mpc_init_counter, const_cast<double*>(bf->root_lin_vel_d), const_cast<double*>(bf->root_ang_vel_d), const_cast<uint8_t*>(bf->movement_mode),
+                       const_cast<uint8_t*>(bf->mpc_active), const_cast<double*>(bf->root_pos_d_z)};
+    if (const char* bad = invalid_sensor_call(h, &sn->sensor, n, si)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (const char* bad = invalid_command_call(&sn->command, n, ci)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (a1mpc_status st = invalid_tick_call(h, p, nullptr, bf, n, false); st != A1MPC_OK) return st;   // the tick's own refusals, before the front end launches
+    if (n == 0) return A1MPC_OK;
+    A1_HIP(hipSetDevice(h->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
+    A1_ORDER(h, s);
+    if (a1mpc_status st = ensure_sensor_state(h, sn->sensor.imu_window, s); st != A1MPC_OK) return st;
+    launch_sensor(h, sn->sensor.imu_window, n, si, s);
+    launch_command(sn->command, n, ci, s);
+    A1_HIP(hipGetLastError());
+    A1_MARK(h, s);
     return control_tick_impl(h, p, nullptr, bf, n, hip_stream);
 }
 // a1mpc_control_tick_device with the preview kernel between the contacts / terrain stage and the MPC launch; {0, 0, *} is a1mpc_control_tick_device

@@ -57,6 +57,23 @@ class BalanceTick(C.Structure):  # a1mpc_balance_tick: what a1mpc_control_tick_b
     _fields_ = [("gains", BalanceGains), ("qp", BalanceConfig), ("root_pos_d", C.c_void_p), ("root_acc", C.c_void_p), ("f_world", C.c_void_p)]
 
 
+class SensorConfig(C.Structure):  # a1mpc_sensor_config: the window of the six IMU filters (S/GazeboA1ROS.cpp:99-104)
+    _fields_ = [("imu_window", C.c_int32)]
+
+
+class CommandConfig(C.Structure):  # a1mpc_command_config: the constants of main_update's first half (S/GazeboA1ROS.cpp:124-188) and the mpc_init_counter gate
+    _fields_ = [("body_height_max", C.c_double), ("body_height_min", C.c_double), ("kp_linear_lock_x", C.c_double), ("kp_linear_lock_y", C.c_double),
+                ("lock_speed", C.c_double), ("mpc_init_ticks", C.c_int32)]
+
+
+TICK_SENSOR_POINTERS = ("quat", "imu_acc_raw", "imu_gyro_raw", "cmd", "mode_toggle", "body_height", "ctrl_state", "root_pos_d", "kp_linear_xy", "mpc_init_counter")
+COMMAND_STATE_FIELDS = ("body_height", "ctrl_state", "root_euler_d", "root_pos_d", "kp_linear_xy", "mpc_init_counter")   # carried by the caller, in the C ABI's order
+
+
+class TickSensors(C.Structure):  # a1mpc_tick_sensors: what a1mpc_control_tick_sensors_device takes beside TickParams / TickBuffers (device pointers)
+    _fields_ = [("sensor", SensorConfig), ("command", CommandConfig)] + [(k, C.c_void_p) for k in TICK_SENSOR_POINTERS]
+
+
 TICK_BUFFER_FIELDS = ("joint_pos", "joint_vel", "R_world", "R_z", "root_euler", "root_ang_vel", "imu_acc", "imu_ang_vel", "foot_force", "movement_mode", "mpc_active",
                       "root_lin_vel_d", "root_ang_vel_d", "root_pos_d_z", "gait_counter_speed", "torques_gravity", "gait_counter", "foot_pos_start", "foot_pos_rel_last_time",
                       "foot_pos_target_last_time", "root_euler_d", "joint_torques", "root_pos", "root_lin_vel", "estimated_contacts", "plan_contacts", "contacts", "foot_pos_rel",
@@ -68,7 +85,9 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_balance_gains", "a1mpc_balance_wrench_batch", "a1mpc_balance_wrench_batch_device", "a1mpc_balance_solve_batch_device", "a1mpc_contacts_batch",
+EXPORTS = ["a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
+           "a1mpc_command_batch", "a1mpc_command_batch_device", "a1mpc_control_tick_sensors_device", "a1mpc_balance_wrench_kp_batch", "a1mpc_balance_wrench_kp_batch_device",
+           "a1mpc_default_balance_gains", "a1mpc_balance_wrench_batch", "a1mpc_balance_wrench_batch_device", "a1mpc_balance_solve_batch_device", "a1mpc_contacts_batch",
            "a1mpc_contacts_batch_device", "a1mpc_control_tick_balance_device",
            "a1mpc_horizon_states_batch", "a1mpc_horizon_states_batch_device", "a1mpc_horizon_states_ticks_batch", "a1mpc_horizon_states_ticks_batch_device",
            "a1mpc_horizon_preview_footholds_batch", "a1mpc_horizon_preview_footholds_batch_device", "a1mpc_control_tick_preview_footholds_device",
@@ -202,6 +221,19 @@ def load_library(path=None):
         lib.a1mpc_contacts_batch_device.argtypes = [vp, C.POINTER(ContactConfig), i32] + [vpp] * 6 + [vpp]; lib.a1mpc_contacts_batch_device.restype = C.c_int
         lib.a1mpc_control_tick_balance_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(BalanceTick), C.POINTER(TickBuffers), i32, vp]
         lib.a1mpc_control_tick_balance_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_sensors_device"):   # (the sensor / command front end; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_balance_wrench_kp_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 11; lib.a1mpc_balance_wrench_kp_batch.restype = C.c_int
+        lib.a1mpc_balance_wrench_kp_batch_device.argtypes = [vp, C.POINTER(BalanceGains), i32] + [vpp] * 11 + [vpp]; lib.a1mpc_balance_wrench_kp_batch_device.restype = C.c_int
+        lib.a1mpc_default_sensor_config.argtypes = [C.POINTER(SensorConfig)]; lib.a1mpc_default_sensor_config.restype = None
+        lib.a1mpc_default_command_config.argtypes = [C.POINTER(CommandConfig)]; lib.a1mpc_default_command_config.restype = None
+        lib.a1mpc_reset_sensor_state.argtypes = [vp]; lib.a1mpc_reset_sensor_state.restype = C.c_int
+        lib.a1mpc_sensor_frontend_batch.argtypes = [vp, C.POINTER(SensorConfig), i32] + [dp] * 9; lib.a1mpc_sensor_frontend_batch.restype = C.c_int
+        lib.a1mpc_sensor_frontend_batch_device.argtypes = [vp, C.POINTER(SensorConfig), i32] + [vpp] * 9 + [vpp]; lib.a1mpc_sensor_frontend_batch_device.restype = C.c_int
+        lib.a1mpc_command_batch.argtypes = [vp, C.POINTER(CommandConfig), i32, dp, u8p, dp, C.c_double, dp, u8p, dp, dp, dp, i32p, dp, dp, u8p, u8p, dp]
+        lib.a1mpc_command_batch.restype = C.c_int
+        lib.a1mpc_command_batch_device.argtypes = [vp, C.POINTER(CommandConfig), i32, vpp, vpp, vpp, C.c_double] + [vpp] * 11 + [vpp]; lib.a1mpc_command_batch_device.restype = C.c_int
+        lib.a1mpc_control_tick_sensors_device.argtypes = [vp, C.POINTER(TickParams), C.POINTER(TickSensors), C.POINTER(TickBuffers), i32, vpp]
+        lib.a1mpc_control_tick_sensors_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_last_tick_stage_cycles"):  # (round 5; an older build bound by hand for an A/B may lack it)
         lib.a1mpc_last_tick_stage_cycles.argtypes = [vp, dp, C.POINTER(C.c_int32)]; lib.a1mpc_last_tick_stage_cycles.restype = C.c_int
     lib.a1mpc_set_schedule.argtypes = [vp, i32]; lib.a1mpc_set_schedule.restype = C.c_int
@@ -250,6 +282,11 @@ def _ip(a):
 
 def _u8p(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _dev(t):
+    """a device pointer: a torch tensor, an integer address, or None"""
+    return None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
 
 
 def _f64(a, shape):
@@ -550,6 +587,108 @@ class Engine:
                                                         ptr(d_root_euler_d), ptr(d_root_euler), ptr(d_root_ang_vel_d), ptr(d_root_ang_vel), ptr(d_R), ptr(d_root_acc),
                                                         C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_balance_wrench_batch_device")
+
+    def balance_wrench_kp(self, kp_linear_xy, root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, root_ang_vel, R, gains=None):
+        """root_acc (n, 6) of a1mpc_balance_wrench_kp_batch: balance_wrench with kp_linear[0:2] per robot (kp_linear_xy (n, 2), the command stage's)"""
+        g = self.balance_gains() if gains is None else gains
+        kp = _f64(kp_linear_xy, (-1, 2)); n = kp.shape[0]
+        arrs = [kp] + [_f64(a, (n, 3)) for a in (root_pos_d, root_pos, root_lin_vel_d, root_lin_vel, root_euler_d, root_euler, root_ang_vel_d, root_ang_vel)] + [_f64(R, (n, 9))]
+        acc = np.zeros((n, 6))
+        _check(self.lib, self.lib.a1mpc_balance_wrench_kp_batch(self._h, C.byref(g), n, *[_dp(a) for a in arrs], _dp(acc)), "a1mpc_balance_wrench_kp_batch")
+        return acc
+
+    def balance_wrench_kp_device(self, n, d_kp_linear_xy, d_root_pos_d, d_root_pos, d_root_lin_vel_d, d_root_lin_vel, d_root_euler_d, d_root_euler, d_root_ang_vel_d,
+                                 d_root_ang_vel, d_R, d_root_acc, gains=None, stream=None):
+        """a1mpc_balance_wrench_kp_batch_device: device pointers (torch tensors), asynchronous on `stream`"""
+        g = self.balance_gains() if gains is None else gains
+        rc = self.lib.a1mpc_balance_wrench_kp_batch_device(self._h, C.byref(g), int(n), *[_dev(t) for t in (d_kp_linear_xy, d_root_pos_d, d_root_pos, d_root_lin_vel_d,
+                                                           d_root_lin_vel, d_root_euler_d, d_root_euler, d_root_ang_vel_d, d_root_ang_vel, d_R, d_root_acc)],
+                                                           C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_balance_wrench_kp_batch_device")
+
+    # ---- the sensor and command front end (gt_pose_callback, imu_callback and the first half of main_update, S/GazeboA1ROS.cpp:235-262, 284-300, 124-188) ----
+    def sensor_config(self, imu_window=None):
+        c = SensorConfig(); self.lib.a1mpc_default_sensor_config(C.byref(c))
+        if imu_window is not None:
+            c.imu_window = int(imu_window)
+        return c
+
+    def command_config(self, **fields):
+        """a1mpc_default_command_config with `fields` overridden"""
+        c = CommandConfig(); self.lib.a1mpc_default_command_config(C.byref(c))
+        for k, v in fields.items():
+            if not hasattr(c, k):
+                raise KeyError(k)
+            setattr(c, k, v)
+        return c
+
+    def sensor_frontend(self, quat, imu_acc_raw, imu_gyro_raw, cfg=None):
+        """a1mpc_sensor_frontend_batch on host arrays: quat (n, 4) as w, x, y, z and the raw IMU sample -> dict(R_world, R_z (n, 9), root_euler, imu_acc, imu_ang_vel,
+        root_ang_vel (n, 3)); the six filters' state of every robot lives in the handle (reset_sensor_state)"""
+        cfg = self.sensor_config() if cfg is None else cfg
+        q = _f64(quat, (-1, 4)); n = q.shape[0]; acc = _f64(imu_acc_raw, (n, 3)); gyro = _f64(imu_gyro_raw, (n, 3))
+        out = {k: np.zeros((n, w)) for k, w in (("R_world", 9), ("R_z", 9), ("root_euler", 3), ("imu_acc", 3), ("imu_ang_vel", 3), ("root_ang_vel", 3))}
+        rc = self.lib.a1mpc_sensor_frontend_batch(self._h, C.byref(cfg), n, _dp(q), _dp(acc), _dp(gyro), *[_dp(v) for v in out.values()])
+        _check(self.lib, rc, "a1mpc_sensor_frontend_batch")
+        return out
+
+    def sensor_frontend_device(self, n, d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_R_world, d_R_z, d_root_euler, d_imu_acc, d_imu_ang_vel, d_root_ang_vel, cfg=None, stream=None):
+        """a1mpc_sensor_frontend_batch_device: device pointers (torch tensors), asynchronous on `stream`"""
+        cfg = self.sensor_config() if cfg is None else cfg
+        rc = self.lib.a1mpc_sensor_frontend_batch_device(self._h, C.byref(cfg), int(n), *[_dev(t) for t in (d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_R_world, d_R_z, d_root_euler,
+                                                         d_imu_acc, d_imu_ang_vel, d_root_ang_vel)], C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_sensor_frontend_batch_device")
+
+    def reset_sensor_state(self):
+        _check(self.lib, self.lib.a1mpc_reset_sensor_state(self._h), "a1mpc_reset_sensor_state")
+
+    @staticmethod
+    def command_state(n):
+        """the command stage's carried state of n robots at the reference's initial values: body_height 0.3 (S/GazeboA1ROS.h:130), joy_cmd_ctrl_state 0, root_euler_d and
+        root_pos_d zero (S/A1CtrlStates.h:35-36), kp_linear[0:2] = the lock values 120 (S/A1CtrlStates.h:273-274, 301), mpc_init_counter 0 (S/A1RobotControl.cpp:25)"""
+        n = int(n)
+        return dict(body_height=np.full(n, 0.3), ctrl_state=np.zeros(n, np.uint8), root_euler_d=np.zeros((n, 3)), root_pos_d=np.zeros((n, 3)),
+                    kp_linear_xy=np.full((n, 2), 120.0), mpc_init_counter=np.zeros(n, np.int32))
+
+    def command(self, cmd, mode_toggle, root_pos, dt, state, cfg=None):
+        """a1mpc_command_batch on host arrays: cmd (n, 6), mode_toggle (n,), root_pos (n, 3); `state` (command_state(n)) is updated IN PLACE; returns
+        dict(root_lin_vel_d, root_ang_vel_d (n, 3), movement_mode, mpc_active (n,) uint8, root_pos_d_z (n,))"""
+        cfg = self.command_config() if cfg is None else cfg
+        c = _f64(cmd, (-1, 6)); n = c.shape[0]; tg = np.ascontiguousarray(mode_toggle, dtype=np.uint8).reshape(n); pos = _f64(root_pos, (n, 3))
+        for k, dt_, shape in (("body_height", np.float64, (n,)), ("ctrl_state", np.uint8, (n,)), ("root_euler_d", np.float64, (n, 3)), ("root_pos_d", np.float64, (n, 3)),
+                              ("kp_linear_xy", np.float64, (n, 2)), ("mpc_init_counter", np.int32, (n,))):
+            a = state[k]
+            assert a.dtype == dt_ and a.flags["C_CONTIGUOUS"] and a.shape == shape, k
+        out = dict(root_lin_vel_d=np.zeros((n, 3)), root_ang_vel_d=np.zeros((n, 3)), movement_mode=np.zeros(n, np.uint8), mpc_active=np.zeros(n, np.uint8), root_pos_d_z=np.zeros(n))
+        rc = self.lib.a1mpc_command_batch(self._h, C.byref(cfg), n, _dp(c), _u8p(tg), _dp(pos), float(dt), _dp(state["body_height"]), _u8p(state["ctrl_state"]),
+                                          _dp(state["root_euler_d"]), _dp(state["root_pos_d"]), _dp(state["kp_linear_xy"]), _ip(state["mpc_init_counter"]),
+                                          _dp(out["root_lin_vel_d"]), _dp(out["root_ang_vel_d"]), _u8p(out["movement_mode"]), _u8p(out["mpc_active"]), _dp(out["root_pos_d_z"]))
+        _check(self.lib, rc, "a1mpc_command_batch")
+        return out
+
+    def command_device(self, n, d_cmd, d_mode_toggle, d_root_pos, dt, d_body_height, d_ctrl_state, d_root_euler_d, d_root_pos_d, d_kp_linear_xy, d_mpc_init_counter,
+                       d_root_lin_vel_d, d_root_ang_vel_d, d_movement_mode, d_mpc_active, d_root_pos_d_z, cfg=None, stream=None):
+        """a1mpc_command_batch_device: device pointers (torch tensors), asynchronous on `stream`"""
+        cfg = self.command_config() if cfg is None else cfg
+        rc = self.lib.a1mpc_command_batch_device(self._h, C.byref(cfg), int(n), _dev(d_cmd), _dev(d_mode_toggle), _dev(d_root_pos), float(dt),
+                                                 *[_dev(t) for t in (d_body_height, d_ctrl_state, d_root_euler_d, d_root_pos_d, d_kp_linear_xy, d_mpc_init_counter, d_root_lin_vel_d,
+                                                                     d_root_ang_vel_d, d_movement_mode, d_mpc_active, d_root_pos_d_z)], C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_command_batch_device")
+
+    def tick_sensors(self, sensor=None, command=None, **pointers):
+        """a TickSensors: default configs unless given, device pointers (torch tensors) for TICK_SENSOR_POINTERS"""
+        ts = TickSensors()
+        ts.sensor = self.sensor_config() if sensor is None else sensor; ts.command = self.command_config() if command is None else command
+        for k in TICK_SENSOR_POINTERS:
+            t = pointers.pop(k)
+            setattr(ts, k, t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        assert not pointers, pointers
+        return ts
+
+    def control_tick_sensors_device(self, params, sensors, buffers, n, stream=None):
+        """a1mpc_control_tick_sensors_device: the sensor stage, the command stage and control_tick_device in one call, from raw inputs (a TickSensors)"""
+        _check(self.lib, self.lib.a1mpc_control_tick_sensors_device(self._h, C.byref(params), C.byref(sensors), C.byref(buffers), int(n),
+                                                                    C.c_void_p(stream) if stream else None), "a1mpc_control_tick_sensors_device")
 
     def balance_solve_device(self, n, d_root_acc, d_R, d_Rz, d_foot, d_contact, d_grf, d_f_world=None, d_iters=None, d_status=None, qp=None, stream=None):
         """a1mpc_balance_solve_batch_device: balance_solve on device pointers (torch tensors), asynchronous on `stream`"""

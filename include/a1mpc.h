@@ -465,6 +465,98 @@ typedef struct a1mpc_balance_tick {
 a1mpc_status a1mpc_control_tick_balance_device(a1mpc_handle h, const a1mpc_tick_params* params, const a1mpc_balance_tick* balance, const a1mpc_tick_buffers* buffers,
                                                int32_t n, void* hip_stream);
 
+/* a1mpc_balance_wrench_batch(_device) with kp_linear[0:2] PER ROBOT: kp_linear_xy (n x 2) replaces gains->kp_linear[0:2], gains->kp_linear[2] and the nine other gains
+ * stay the batch's.  The reference switches kp_linear(0), kp_linear(1) of every robot between 0 (walking with a velocity command: the position target follows the robot)
+ * and kp_linear_lock_x / _y (S/GazeboA1ROS.cpp:172-173, 183-186) -- a1mpc_command_batch's kp_linear_xy, of which this entry is the consumer: with the batch-wide gains
+ * a walking robot on the balance controller is pulled back to its lock point.  A kernel of its own around the wrench kernel's per-robot body; bit-identical to
+ * a1mpc_balance_wrench_batch when every row holds gains->kp_linear[0:2].  Refusals as there, and a null kp_linear_xy. */
+a1mpc_status a1mpc_balance_wrench_kp_batch(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* kp_linear_xy, const double* root_pos_d,
+                                           const double* root_pos, const double* root_lin_vel_d, const double* root_lin_vel, const double* root_euler_d,
+                                           const double* root_euler, const double* root_ang_vel_d, const double* root_ang_vel, const double* R_world, double* root_acc_out);
+a1mpc_status a1mpc_balance_wrench_kp_batch_device(a1mpc_handle h, const a1mpc_balance_gains* gains, int32_t n, const double* d_kp_linear_xy, const double* d_root_pos_d,
+                                                  const double* d_root_pos, const double* d_root_lin_vel_d, const double* d_root_lin_vel, const double* d_root_euler_d,
+                                                  const double* d_root_euler, const double* d_root_ang_vel_d, const double* d_root_ang_vel, const double* d_R_world,
+                                                  double* d_root_acc_out, void* hip_stream);
+
+/*
+ * The sensor and command front end: what the reference's adapter makes of what a simulator or robot provides -- a quaternion, raw IMU samples, a stick command --
+ * BEFORE the chain of a1mpc_control_tick_device starts.  The ROS publishers and subscribers of S/GazeboA1ROS.cpp stay out of scope; the arithmetic inside its
+ * callbacks is a per-robot function of arrays, and is this.
+ *
+ * a1mpc_sensor_frontend_batch(_device), n robots:
+ *   in   quat n x 4 (w, x, y, z; NOT normalised, as in the reference), imu_acc_raw n x 3, imu_gyro_raw n x 3
+ *   out  R_world n x 9 row-major = root_quat.toRotationMatrix() (gt_pose_callback, S/GazeboA1ROS.cpp:258; Eigen's operation order: tx = 2x, twx = tx * w, ...,
+ *        R00 = 1 - (tyy + tzz)); root_euler n x 3 = Utils::quat_to_euler (:259, S/utils/Utils.cpp:7-33, the clamp of t2 included); R_z n x 9 =
+ *        AngleAxisd(yaw, UnitZ) as a matrix (:262); imu_acc, imu_ang_vel n x 3 = the six MovingWindowFilter(5) of imu_callback (:289-298, S/utils/filter.hpp:26-62:
+ *        Neumaier sums, divided by the window length from the first sample on); root_ang_vel n x 3 = R_world * imu_ang_vel (:299) on this call's matrix and filtered
+ *        value, every row sum of three terms left to right.
+ *   Not contracted: everything except atan2, asin, sin and cos is the reference's arithmetic bit for bit (those four are the device library's, their arguments
+ *   bit-identical).  ONE UNPINNED CHOICE: R_z follows Eigen's AngleAxis::toRotationMatrix as published (sin_axis = s * axis, cos1_axis = (1 - c) * axis, the
+ *   off-diagonal pairs tmp -+ sin_axis, the diagonal cos1_axis .* axis + c -- element (2,2) is (1 - c) + c, not a literal 1); no Eigen is at hand where this
+ *   project is built to pin that order against, the two rotation matrices are held to a restatement written from Eigen's source text (tests/frontend_ref.py).
+ *   The filter state lives in the handle, indexed by the robot's position in the batch, allocated on first use; a1mpc_reset_sensor_state clears it (= constructing
+ *   the adapter).  cfg->imu_window runs from 1 to 64 (A1MPC_IMU_WINDOW_MAX); a window other than the one the state was built with, without a reset in between, is
+ *   A1MPC_ERR_INVALID_ARGUMENT.
+ *
+ * a1mpc_command_batch(_device): the first half of main_update, S/GazeboA1ROS.cpp:124-188, branch for branch, and the gate of compute_joint_torques
+ * (S/A1RobotControl.cpp:292-294).
+ *   in   cmd n x 6 = joy_cmd_velx, vely, velz, roll_rate, pitch_rate, yaw_rate after joy_callback's scaling (the axis mapping differs between the Gazebo and the
+ *        hardware adapter and stays with the caller); mode_toggle n (joy_cmd_ctrl_state_change_request); root_pos n x 3 (the previous tick's estimate); dt
+ *   in/out, carried by the caller like gait_counter (A1CtrlStates / adapter members): body_height n (joy_cmd_body_height, initially 0.3, S/GazeboA1ROS.h:130),
+ *        ctrl_state n (joy_cmd_ctrl_state), root_euler_d n x 3, root_pos_d n x 3, kp_linear_xy n x 2 (kp_linear(0), kp_linear(1)), mpc_init_counter n
+ *   out  root_lin_vel_d, root_ang_vel_d n x 3; movement_mode n; mpc_active n: 1 from the call on which the incremented counter reaches mpc_init_ticks;
+ *        root_pos_d_z n: the contiguous copy of root_pos_d[.][2] the tick takes
+ *   body_height += velz * dt (the product rounded first), clamped with >= max / <= min (:124-130); the toggle (:142-147); root_euler_d += rate * dt (:158-160);
+ *   movement_mode 1 in state 1; on the ONE tick that leaves state 1 the xy target is locked to root_pos and kp_linear_xy set to the lock values (:167-173); otherwise
+ *   (:174-176) kp_linear_xy is left as it is; in mode 1, sqrt(vx * vx + vy * vy) > lock_speed refreshes the xy target and zeroes kp_linear_xy, else the lock values (:179-188).
+ *
+ * Both: a null handle, config or array, a non-finite config value or dt, body_height_min > body_height_max, a window out of range or n < 0 is
+ * A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the argument), n > max_batch A1MPC_ERR_BATCH_TOO_LARGE, all before any device call; n == 0 launches nothing.  The
+ * _device entries take device pointers and are asynchronous on `hip_stream` (NULL = the handle's stream); the host entries stage through device memory.
+ */
+#define A1MPC_IMU_WINDOW_MAX 64
+typedef struct a1mpc_sensor_config { int32_t imu_window; } a1mpc_sensor_config;   /* default 5, S/GazeboA1ROS.cpp:99-104 */
+typedef struct a1mpc_command_config {
+    double body_height_max, body_height_min;      /* 0.32, 0.1: JOY_CMD_BODY_HEIGHT_MAX / _MIN, S/A1Params.h:16-17 */
+    double kp_linear_lock_x, kp_linear_lock_y;    /* 120, 120: S/A1CtrlStates.h:273-274, 298-299 */
+    double lock_speed;                            /* 0.05: S/GazeboA1ROS.cpp:180 */
+    int32_t mpc_init_ticks;                       /* 10: S/A1RobotControl.cpp:294 */
+} a1mpc_command_config;
+void a1mpc_default_sensor_config(a1mpc_sensor_config* cfg);
+void a1mpc_default_command_config(a1mpc_command_config* cfg);
+a1mpc_status a1mpc_reset_sensor_state(a1mpc_handle h);
+a1mpc_status a1mpc_sensor_frontend_batch(a1mpc_handle h, const a1mpc_sensor_config* cfg, int32_t n, const double* quat, const double* imu_acc_raw, const double* imu_gyro_raw,
+                                         double* R_world_out, double* R_z_out, double* root_euler_out, double* imu_acc_out, double* imu_ang_vel_out, double* root_ang_vel_out);
+a1mpc_status a1mpc_sensor_frontend_batch_device(a1mpc_handle h, const a1mpc_sensor_config* cfg, int32_t n, const double* d_quat, const double* d_imu_acc_raw,
+                                                const double* d_imu_gyro_raw, double* d_R_world_out, double* d_R_z_out, double* d_root_euler_out, double* d_imu_acc_out,
+                                                double* d_imu_ang_vel_out, double* d_root_ang_vel_out, void* hip_stream);
+a1mpc_status a1mpc_command_batch(a1mpc_handle h, const a1mpc_command_config* cfg, int32_t n, const double* cmd, const uint8_t* mode_toggle, const double* root_pos, double dt,
+                                 double* body_height, uint8_t* ctrl_state, double* root_euler_d, double* root_pos_d, double* kp_linear_xy, int32_t* mpc_init_counter,
+                                 double* root_lin_vel_d_out, double* root_ang_vel_d_out, uint8_t* movement_mode_out, uint8_t* mpc_active_out, double* root_pos_d_z_out);
+a1mpc_status a1mpc_command_batch_device(a1mpc_handle h, const a1mpc_command_config* cfg, int32_t n, const double* d_cmd, const uint8_t* d_mode_toggle, const double* d_root_pos,
+                                        double dt, double* d_body_height, uint8_t* d_ctrl_state, double* d_root_euler_d, double* d_root_pos_d, double* d_kp_linear_xy,
+                                        int32_t* d_mpc_init_counter, double* d_root_lin_vel_d_out, double* d_root_ang_vel_d_out, uint8_t* d_movement_mode_out,
+                                        uint8_t* d_mpc_active_out, double* d_root_pos_d_z_out, void* hip_stream);
+/* The control tick from RAW inputs in one call: the sensor stage, the command stage (dt = params->control_dt, root_pos = buffers->root_pos, root_euler_d =
+ * buffers->root_euler_d), then exactly a1mpc_control_tick_device, back to back on `hip_stream` with no host round trip; bit-identical to calling
+ * a1mpc_sensor_frontend_batch_device, a1mpc_command_batch_device and a1mpc_control_tick_device by hand.  Of a1mpc_tick_buffers, ELEVEN input fields become outputs of
+ * the call -- R_world, R_z, root_euler, root_ang_vel, imu_acc, imu_ang_vel, movement_mode, mpc_active, root_lin_vel_d, root_ang_vel_d, root_pos_d_z: the caller
+ * supplies the storage, the front end writes it, the tick reads it -- and root_euler_d is integrated by the command stage before the terrain stage overwrites its
+ * pitch.  Every refusal of the three entries is made before the first launch.  a1mpc_last_control_tick_ms reports the tick behind the front end.
+ * Out of scope: the preview / foothold ticks, and the balance tick (which would also need a1mpc_balance_wrench_kp_batch inside it). */
+typedef struct a1mpc_tick_sensors {   /* DEVICE pointers, n robots each */
+    a1mpc_sensor_config sensor; a1mpc_command_config command;
+    const double *quat, *imu_acc_raw, *imu_gyro_raw;   /* n x 4, n x 3, n x 3 */
+    const double* cmd;                                 /* n x 6 */
+    const uint8_t* mode_toggle;                        /* n */
+    double* body_height;                               /* in/out from here on: n */
+    uint8_t* ctrl_state;                               /* n */
+    double *root_pos_d, *kp_linear_xy;                 /* n x 3, n x 2 */
+    int32_t* mpc_init_counter;                         /* n */
+} a1mpc_tick_sensors;
+a1mpc_status a1mpc_control_tick_sensors_device(a1mpc_handle h, const a1mpc_tick_params* params, const a1mpc_tick_sensors* sensors, const a1mpc_tick_buffers* buffers,
+                                               int32_t n, void* hip_stream);
+
 /*
  * Gait-aware horizon: the device-side PRODUCER of the two inputs a1mpc_solve_batch_strided takes beyond the reference controller's -- a contact schedule over the
  * horizon and per-step feet -- from the state a control tick already holds on the device (gait counters, contacts, feet, the velocity command).
