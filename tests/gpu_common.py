@@ -67,11 +67,12 @@ FORCE_EKF = np.array([-5.0, 0.0, np.nextafter(50.0, 0.0), 50.0, 100.0, 250.0])  
 FORCE_TICK = np.unique(np.concatenate([FORCE_CONTACT, FORCE_EKF]))                    # one foot_force array feeds both stages of the control tick
 
 
-def gait_cycle_fleet(n, speeds=(2.0, 1.5, 3.0, 2.0), stagger_ticks=7):
-    """(gait_counter (n, 4), gait_counter_speed (n, 4)): leg l of every robot runs at speeds[l]; robot b starts stagger_ticks * b ticks after the reset pattern.  At any tick
-    some robot of the fleet is at a lift-off (120), the early-contact mark (180), or the wrap (0)."""
+def gait_cycle_fleet(n, speeds=(2.0, 1.5, 3.0, 2.0), stagger_ticks=7, per_gait=PER_GAIT, reset=GAIT_RESET):
+    """(gait_counter (n, 4), gait_counter_speed (n, 4)): leg l of every robot runs at speeds[l]; robot b starts stagger_ticks * b ticks after the reset pattern `reset` of
+    a gait with period per_gait.  At any tick some robot of the fleet is at a lift-off, at the early-contact mark or at the wrap (the reference's gait, the default: 120,
+    180 and 0)."""
     spd = np.tile(np.asarray(speeds, dtype=np.float64), (n, 1))
-    gc = np.fmod(GAIT_RESET + spd * float(stagger_ticks) * np.arange(n, dtype=np.float64)[:, None], PER_GAIT)
+    gc = np.fmod(np.asarray(reset, dtype=np.float64) + spd * float(stagger_ticks) * np.arange(n, dtype=np.float64)[:, None], per_gait)
     return gc, spd
 
 
@@ -85,35 +86,41 @@ def stand_timetable(n, ticks):
     return np.where(stand, 0, 1).astype(np.uint8)
 
 
-def gait_loop(gc, spd, mm):
+def gait_loop(gc, spd, mm, per_gait=PER_GAIT, per_swing=PER_SWING, reset=GAIT_RESET):
     """update_plan's counter rule as plain numpy (S/A1RobotControl.cpp:150-164): -> (gait_counter, plan_contacts) after one tick with movement_mode mm (n)"""
     walk = np.asarray(mm).astype(bool)[:, None]
-    g = np.where(walk, np.fmod(gc + spd, PER_GAIT), GAIT_RESET)
-    return g, np.where(walk, g <= PER_SWING, True).astype(np.uint8)
+    g = np.where(walk, np.fmod(gc + spd, per_gait), np.asarray(reset, dtype=np.float64))
+    return g, np.where(walk, g <= per_swing, True).astype(np.uint8)
 
 
-def gait_counts(gc0, spd, mm_table):
-    """the counters after each tick of the timetable (ticks, n, 4) and hits = {x: how often a counter of a walking robot is exactly x after its increment}"""
+def gait_counts(gc0, spd, mm_table, per_gait=PER_GAIT, per_swing=PER_SWING, reset=GAIT_RESET, early_mark=None):
+    """the counters after each tick of the timetable (ticks, n, 4) and hits = {x: how often a counter of a walking robot is exactly x after its increment} for x = the
+    lift-off mark (per_swing), the early-contact mark (1.5 x the CONTACT stage's counter_per_swing; default 1.5 * per_swing) and the wrap (0)"""
     gc = gc0.copy(); seq = []
     for mm in mm_table:
-        gc, _ = gait_loop(gc, spd, mm); seq.append(gc)
+        gc, _ = gait_loop(gc, spd, mm, per_gait, per_swing, reset); seq.append(gc)
     seq = np.array(seq); walking = np.asarray(mm_table).astype(bool)[:, :, None]
-    return seq, {x: int(((seq == x) & walking).sum()) for x in (PER_SWING, 1.5 * PER_SWING, 0.0)}
+    early_mark = 1.5 * per_swing if early_mark is None else early_mark
+    return seq, {x: int(((seq == x) & walking).sum()) for x in (float(per_swing), float(early_mark), 0.0)}
 
 
-def assert_thresholds_are_hit(gc0, spd, mm_table):
-    """The input-side assertion of the gait-cycle tests, made before any kernel output is looked at: over the run the counters equal 120, 180 and 0 at least n times each
-    (once per robot on average).  A run shorter than the fastest leg's cycle (80 ticks at speed 3) cannot reach that; there every single tick must hit each of the three marks
-    on some robot, and the count must reach n * ticks / 160 -- what the slowest leg (160 ticks per cycle at speed 1.5) alone contributes to a uniformly staggered fleet."""
+def assert_thresholds_are_hit(gc0, spd, mm_table, per_gait=PER_GAIT, per_swing=PER_SWING, reset=GAIT_RESET, early_mark=None):
+    """The input-side assertion of the gait-cycle tests, made before any kernel output is looked at: over the run the counters equal the lift-off mark (per_swing), the
+    early-contact mark (early_mark, default 1.5 * per_swing) and the wrap (0) at least n times each, once per robot on average.  A run shorter than the fastest leg's cycle
+    (per_gait over the largest speed) cannot reach that; there every single tick must hit each of the three marks on some robot, and the count must reach n * ticks over
+    the slowest leg's cycle length -- what that leg alone contributes to a uniformly staggered fleet.  The reference's gait with speeds (2, 1.5, 3, 2), the defaults: marks
+    120 / 180 / 0, cycles of 80 and 160 ticks."""
     ticks, n = np.asarray(mm_table).shape
-    seq, hits = gait_counts(gc0, spd, mm_table)
-    print(f"n {n} ticks {ticks}: gait_counter == 120 / 180 / 0 after the increment {hits[120.0]} / {hits[180.0]} / {hits[0.0]} times")
-    if ticks >= 80:
+    seq, hits = gait_counts(gc0, spd, mm_table, per_gait, per_swing, reset, early_mark)
+    lift, early = float(per_swing), float(1.5 * per_swing if early_mark is None else early_mark)
+    fastest, slowest = int(per_gait / np.max(spd)), int(per_gait / np.min(spd))
+    print(f"n {n} ticks {ticks}: gait_counter == {lift:g} / {early:g} / 0 after the increment {hits[lift]} / {hits[early]} / {hits[0.0]} times")
+    if ticks >= fastest:
         assert min(hits.values()) >= n, hits
     else:
         walking = np.asarray(mm_table).astype(bool)[:, :, None]
         for x in hits:
-            assert ((seq == x) & walking).any(axis=(1, 2)).all() and hits[x] >= n * ticks // 160, (x, hits)
+            assert ((seq == x) & walking).any(axis=(1, 2)).all() and hits[x] >= n * ticks // slowest, (x, hits)
     return seq, hits
 
 
@@ -168,7 +175,6 @@ class TickChain:
         import torch
         self.eng, self.prm, self.n, self.st, self.pv, self.footholds = eng, prm, n, stream, preview, footholds
         self.sp = C.c_void_p(stream.cuda_stream)
-        self.k = {k: np.array(getattr(prm, k)) for k in ("kp_foot", "kd_foot", "km_foot", "rho_fix", "rho_opt")}
         h = eng.horizon; dev = torch.device("cuda", 0)
         self.sched_d = torch.zeros((n, 4 * h), dtype=torch.uint8, device=dev) if preview is not None and preview.contact_schedule else None
         self.feet_d = torch.zeros((n, 12 * h), dtype=torch.float64, device=dev) if preview is not None and preview.foot_preview else None
@@ -178,12 +184,13 @@ class TickChain:
         import torch
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         dp_ = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        n, prm, sp, st, pv, k = self.n, self.prm, self.sp, self.st, self.pv, self.k
+        n, prm, sp, st, pv = self.n, self.prm, self.sp, self.st, self.pv
+        k = {f: np.array(getattr(prm, f)) for f in ("kp_foot", "kd_foot", "km_foot", "rho_fix", "rho_opt")}   # (read at every tick: the caller may change them between ticks)
         s7, o7, b7, j7, L, H_ = w["state"], w["outs"], w["u8"], w["i32"], self.eng.lib, self.eng._h
         rcs = [L.a1mpc_leg_state_batch_device(H_, n, ptr(inp["joint_pos"]), ptr(inp["joint_vel"]), ptr(inp["R_world"]), ptr(s7["root_pos"]), ptr(s7["root_lin_vel"]),
                                               dp_(k["rho_fix"]), dp_(k["rho_opt"]), ptr(o7["foot_pos_rel"]), ptr(o7["j_foot_blocks"]), ptr(o7["foot_vel_rel"]),
                                               ptr(o7["foot_pos_abs"]), ptr(o7["foot_vel_abs"]), ptr(o7["foot_pos_world"]), ptr(o7["foot_vel_world"]), sp),
-               L.a1mpc_ekf_update_batch_device(H_, n, prm.control_dt, 1, ptr(inp["movement_mode"]), ptr(inp["foot_force"]), ptr(inp["R_world"]), ptr(inp["imu_acc"]),
+               L.a1mpc_ekf_update_batch_device(H_, n, prm.control_dt, prm.assume_flat_ground, ptr(inp["movement_mode"]), ptr(inp["foot_force"]), ptr(inp["R_world"]), ptr(inp["imu_acc"]),
                                                ptr(inp["imu_ang_vel"]), ptr(o7["foot_pos_rel"]), ptr(o7["foot_vel_rel"]), ptr(s7["root_pos"]), ptr(s7["root_lin_vel"]),
                                                ptr(b7["estimated_contacts"]), sp),
                L.a1mpc_update_plan_batch_device(H_, C.byref(prm.gait), n, ptr(inp["movement_mode"]), ptr(s7["gait_counter"]), ptr(inp["gait_counter_speed"]),
@@ -221,44 +228,63 @@ class TickChain:
 
 
 # ---- N2b at its thresholds: the same rows for the GPU entry (tests/test_gpu_gait_cycle.py) and the host-compiled kernel text (tests/test_n2b_host.py) ----
-_UP180, _UP30 = np.nextafter(180.0, np.inf), np.nextafter(30.0, np.inf)
-# per tick (gait_counter, plan_contact, foot_force, the contact the reference computes: S/A1RobotControl.cpp:256-271).  An early contact needs gc > 180 AND ff > 30 and is
-# kept until gc <= 180 clears it, whatever the force does meanwhile.
-CONTACT_SCRIPTS = [
-    # the early-contact flag from tick to tick: set, kept at a low force up to the wrap, cleared in stance, NOT set again at 180 exactly
-    [(182.0, 0, 80.0, 1), (184.0, 0, 5.0, 1), (238.0, 0, 5.0, 1), (0.0, 1, 5.0, 1), (122.0, 0, 5.0, 0), (180.0, 0, 80.0, 0)],
-    # the two comparisons on their own: 180 / the next double, 30 / the next double (the 180 row in between clears the flag)
-    [(180.0, 0, 80.0, 0), (_UP180, 0, 80.0, 1), (180.0, 0, 80.0, 0), (182.0, 0, 30.0, 0), (182.0, 0, _UP30, 1), (182.0, 0, 0.0, 1)],
-]
+# per tick (gait_counter, plan_contact, foot_force, the contact the reference computes: S/A1RobotControl.cpp:256-271).  An early contact needs gc above the early-contact
+# mark AND ff above foot_force_low, and is kept until a gc at or below the mark clears it, whatever the force does meanwhile.
+def contact_scripts(per_swing=PER_SWING, low=30.0, contact_per_swing=None, per_gait=PER_GAIT):
+    """the two six-tick scripts for a gait whose legs lift off above per_swing, with the early-contact mark m = 1.5 x contact_per_swing (default per_swing) and the force
+    threshold `low`: every counter is m, the double above it, or a whole number of counts on the stated side of m and per_swing, the last one two counts before the wrap"""
+    m = 1.5 * (per_swing if contact_per_swing is None else contact_per_swing)
+    up_m, up_low = np.nextafter(m, np.inf), np.nextafter(low, np.inf)
+    swing_below = per_swing + 2.0   # a swing counter at or below the mark (122 by default)
+    assert per_swing < swing_below <= m and m + 4.0 < per_gait - 2.0
+    return [
+        # the early-contact flag from tick to tick: set, kept at a low force up to the wrap, cleared in stance, NOT set again at the mark exactly
+        [(m + 2.0, 0, low + 50.0, 1), (m + 4.0, 0, 5.0, 1), (per_gait - 2.0, 0, 5.0, 1), (0.0, 1, 5.0, 1), (swing_below, 0, 5.0, 0), (m, 0, low + 50.0, 0)],
+        # the two comparisons on their own: the mark / the next double, the force threshold / the next double (the mark row in between clears the flag)
+        [(m, 0, low + 50.0, 0), (up_m, 0, low + 50.0, 1), (m, 0, low + 50.0, 0), (m + 2.0, 0, low, 0), (m + 2.0, 0, up_low, 1), (m + 2.0, 0, 0.0, 1)],
+    ]
+
+
+CONTACT_SCRIPTS = contact_scripts()   # the reference's gait: 180 and the next double, 30 N and the next double
 Z_STANDING = np.array([0.1, np.nextafter(0.1, 1.0), 0.3])    # root_pos_z > 0.1 is "standing": 0.1 itself is not
 
 
-def contact_threshold_run(step, oracle, n, angle_tol):
+def contact_threshold_run(step, oracle, n, angle_tol, scripts=None, adapt=1, **contact_kw):
     """The scripts above tiled over n robots x 4 legs (robot b, leg l runs script (b + l) % 2) for six ticks, root_pos_z cycling through Z_STANDING, feet on the plane
     z = 0.2 x - 0.3.  First the ORACLE is held to the tabulated contacts and to the standing rule, then `step` (gait_counter, plan, foot_force, foot_pos_abs, root_pos_z,
-    pitch -> dict) to the oracle: contacts and filtered positions bit for bit, terrain angle and pitch within angle_tol."""
+    pitch -> dict) to the oracle: contacts and filtered positions bit for bit, terrain angle and pitch within angle_tol.  scripts / contact_kw (counter_per_swing,
+    foot_force_low of oracle.contact_terrain_step): another contact config; adapt = 0: use_terrain_adapt off, the pitch must come back bit-unchanged.
+    -> the worst angle / pitch distance"""
+    scripts = CONTACT_SCRIPTS if scripts is None else scripts
     which = (np.arange(n)[:, None] + np.arange(4)[None, :]) % 2
     z = Z_STANDING[np.arange(n) % 3]
     xy = np.outer([0.2, 0.2, -0.2, -0.2], [1.0, 0.0]) + np.outer([1, -1, 1, -1], [0.0, 0.13])
     foot = np.tile(np.c_[xy, 0.2 * xy[:, 0] - 0.3].reshape(12), (n, 1))
     states = [oracle.contact_state() for _ in range(n)]
     pitch_k = np.full(n, 0.125); pitch_o = np.full(n, 0.125)
-    seen = set()
+    seen = set(); worst = 0.0
     for t in range(6):
-        row = np.array([[CONTACT_SCRIPTS[s][t] for s in w] for w in which])   # (n, 4, 4)
+        row = np.array([[scripts[s][t] for s in w] for w in which])   # (n, 4, 4)
         gc, plan, ff, expect = row[:, :, 0], row[:, :, 1].astype(np.uint8), row[:, :, 2], row[:, :, 3].astype(np.uint8)
-        ref = [oracle.contact_terrain_step(states[b], gc[b], plan[b], ff[b], foot[b], z[b], pitch_o[b]) for b in range(n)]
+        ref = [oracle.contact_terrain_step(states[b], gc[b], plan[b], ff[b], foot[b], z[b], pitch_o[b], use_terrain_adapt=adapt, **contact_kw) for b in range(n)]
         ct_o = np.array([r[0] for r in ref]); rec_o = np.array([r[1] for r in ref]); ang_o = np.array([r[2] for r in ref]); pitch_o = np.array([r[3] for r in ref])
         assert np.array_equal(ct_o, expect), (t, np.argwhere(ct_o != expect)[:4])
-        assert (ang_o[z <= 0.1] == 0.0).all() and (pitch_o[z <= 0.1] == 0.0).all() and (ang_o[z > 0.1] > 0.0).all(), t   # z = 0.1: no angle is filtered, the pitch is +-0
+        if adapt:
+            assert (ang_o[z <= 0.1] == 0.0).all() and (pitch_o[z <= 0.1] == 0.0).all() and (ang_o[z > 0.1] > 0.0).all(), t   # z = 0.1: no angle is filtered, the pitch is +-0
+        else:
+            assert (ang_o[z <= 0.1] == 0.0).all() and (ang_o[z > 0.1] > 0.0).all() and (pitch_o == 0.125).all(), t
         seen |= set(expect.ravel().tolist())
         out = step(gc, plan, ff, foot, z, pitch_k); pitch_k = out["root_euler_d_pitch"]
         assert np.array_equal(out["contacts"], ct_o), (t, np.argwhere(out["contacts"] != ct_o)[:4])
         assert np.array_equal(out["foot_pos_recent_contact"], rec_o), t
         da, dp = np.abs(out["terrain_angle"] - ang_o).max(), np.abs(pitch_k - pitch_o).max()
+        worst = max(worst, da, dp)
         assert da <= angle_tol and dp <= angle_tol, (t, da, dp)
         assert (out["terrain_angle"][z <= 0.1] == 0.0).all() and (out["terrain_angle"][z > 0.1] > 0.0).all(), t
+        if not adapt:
+            assert (pitch_k == 0.125).all(), t
     assert seen == {0, 1}
+    return worst
 
 
 def steep_plane_run(step, oracle, angle_tol, n=8, ticks=110):
@@ -378,3 +404,130 @@ def held_to_oracle(out, ref, x87_solve, case, label=""):
         assert d_e <= 5.0 * d_o + TOL_FORCE_N, (label, case, rows)
     worst_ratio = max([r[2] / max(r[3], 1e-300) for r in rows], default=0.0)
     return dict(resolved=int(len(cand)), worst=float(d.max()), worst_ratio=float(worst_ratio))
+
+
+# ---- the caller-side kernels and control ticks at non-default parameters (tests/test_gpu_caller_side_params.py, and on the CPU tests/test_ref_pin.py, tests/test_n2b_host.py) ----
+# Set A: every quantity that exists twice is different in its two places (gait.counter_per_swing 120 / contact.counter_per_swing 100, gait.control_dt 0.004 / control_dt
+# 0.002) and nothing is at the reference's default.  Set B: another period, proportional (320 / 160 in both configs, both dt 0.005): the counters pass 240 and the swing spline
+# reaches 1.  The counters are exact multiples of the speeds below and land on each set's lift-off mark (gait.counter_per_swing), early-contact mark (1.5 x
+# contact.counter_per_swing) and wrap: every mark minus every reset value is a multiple of 10, and every speed divides 10.
+PARAM_SPEEDS = (2.0, 2.5, 5.0, 10.0)
+_RHO_FIX_A = np.array([[0.19, 0.05, 0.09, 0.25, 0.27], [0.17, -0.045, -0.08, 0.24, 0.26], [-0.185, 0.052, 0.085, 0.26, 0.28], [-0.175, -0.048, -0.088, 0.245, 0.265]])
+PARAM_SET_A = dict(
+    name="A", counter_per_gait=200.0, counter_per_swing=120.0, gait_dt=0.004, foot_delta_x_limit=0.06, foot_delta_y_limit=0.14,
+    default_foot_pos=np.array([0.19, 0.14, -0.33, 0.16, -0.17, -0.36, -0.18, 0.13, -0.31, -0.15, -0.16, -0.38]), gait_counter_reset=(10.0, 110.0, 90.0, 0.0),
+    contact_per_swing=100.0, foot_force_low=45.0, control_dt=0.002, assume_flat_ground=0, kp_foot=(250.0, 350.0, 450.0), kd_foot=(6.0, 7.0, 9.0), km_foot=(0.2, 0.05, 0.08),
+    rho_fix=_RHO_FIX_A, rho_opt=np.random.default_rng(20).normal(0, 0.01, (4, 3)))
+PARAM_SET_B = dict(PARAM_SET_A, name="B", counter_per_gait=320.0, counter_per_swing=160.0, contact_per_swing=160.0, gait_dt=0.005, control_dt=0.005)
+PARAM_SETS = dict(A=PARAM_SET_A, B=PARAM_SET_B)
+A1_REACH = 0.1805 + 0.047 + 0.0838 + 0.21 + 0.21                     # |ox| + |oy| + |d| + lt + lc of the A1's legs
+LEG_BAR_SCALE = float(np.abs(_RHO_FIX_A).sum(axis=1).max() / A1_REACH)   # the leg bars (1e-14 positions / Jacobians, 1e-13 velocities) grow with the largest reach
+
+
+def early_mark(ps):
+    return 1.5 * ps["contact_per_swing"]
+
+
+def gait_kw(ps):
+    """the keyword arguments of gait_cycle_fleet / gait_loop / gait_counts / assert_thresholds_are_hit for a parameter set"""
+    return dict(per_gait=ps["counter_per_gait"], per_swing=ps["counter_per_swing"], reset=np.array(ps["gait_counter_reset"]))
+
+
+def force_bar(ps):
+    """the swing legs' foot-force bar: 1e-9 at kp <= 400 and kd / dt = 3200, scaled where the gains scale the output"""
+    return 1e-9 * max(1.0, max(ps["kp_foot"]) / 400.0, (max(ps["kd_foot"]) / ps["control_dt"]) / 3200.0)
+
+
+def oracle_gait(oracle, ps, **over):
+    """oracle.gait_params of a set; over: single fields put back (the sensitivity preconditions)"""
+    kw = dict(default_foot_pos=ps["default_foot_pos"], counter_per_gait=ps["counter_per_gait"], counter_per_swing=ps["counter_per_swing"], control_dt=ps["gait_dt"],
+              dx=ps["foot_delta_x_limit"], dy=ps["foot_delta_y_limit"], reset=ps["gait_counter_reset"])
+    kw.update(over)
+    return oracle.gait_params(kw.pop("default_foot_pos"), **kw)
+
+
+def gait_config(E, ps):
+    g = E.GaitConfig()
+    g.counter_per_gait, g.counter_per_swing, g.control_dt = ps["counter_per_gait"], ps["counter_per_swing"], ps["gait_dt"]
+    g.foot_delta_x_limit, g.foot_delta_y_limit = ps["foot_delta_x_limit"], ps["foot_delta_y_limit"]
+    g.default_foot_pos[:] = list(ps["default_foot_pos"]); g.gait_counter_reset[:] = list(ps["gait_counter_reset"])
+    return g
+
+
+def contact_config(E, ps, adapt=1):
+    c = E.ContactConfig()
+    c.counter_per_swing, c.foot_force_low, c.use_terrain_adapt = ps["contact_per_swing"], ps["foot_force_low"], int(adapt)
+    return c
+
+
+def tick_params(E, ps, adapt=1):
+    """a1mpc_tick_params of a set, every field written (nothing is taken from a1mpc_default_tick_params)"""
+    p = E.TickParams()
+    p.gait = gait_config(E, ps); p.contact = contact_config(E, ps, adapt)
+    p.control_dt, p.assume_flat_ground = ps["control_dt"], int(ps["assume_flat_ground"])
+    p.kp_foot[:] = list(ps["kp_foot"]); p.kd_foot[:] = list(ps["kd_foot"]); p.km_foot[:] = list(ps["km_foot"])
+    p.rho_fix[:] = list(np.asarray(ps["rho_fix"]).reshape(20)); p.rho_opt[:] = list(np.asarray(ps["rho_opt"]).reshape(12))
+    return p
+
+
+def force_values(ps):
+    """foot_force values ON the thresholds of a set's contact stage (foot_force_low) and of the EKF's contact estimate (50 N)"""
+    low = ps["foot_force_low"]
+    return np.unique(np.concatenate([[0.0, low, np.nextafter(low, np.inf), low + 50.0], FORCE_EKF]))
+
+
+def assert_sensitive(label, full, variants):
+    """The sensitivity precondition, on the YARDSTICK's results (oracle / numpy), before any kernel output is read: `full` is the tuple of compared arrays (first axis = robots)
+    at the full parameter set, variants[name] the same tuple with the one parameter `name` put back to its default.  Every variant must differ from `full` on at least one
+    compared element -- or the test could not notice a kernel that ignored that parameter.  Prints the share of robots that differ; -> {name: share}"""
+    shares = {}
+    for name, var in variants.items():
+        n = len(np.asarray(full[0]))
+        differ = np.zeros(n, bool)
+        for a, b in zip(full, var):
+            a, b = np.asarray(a, dtype=np.float64).reshape(n, -1), np.asarray(b, dtype=np.float64).reshape(n, -1)
+            differ |= ~((a == b) | (np.isnan(a) & np.isnan(b))).all(axis=1)
+        shares[name] = float(differ.mean())
+    print(f"{label}: share of robots whose yardstick result changes when one parameter goes back to its default: " + ", ".join(f"{k} {v:.2f}" for k, v in shares.items()))
+    dead = [k for k, v in shares.items() if v == 0.0]
+    assert not dead, (label, dead)
+    return shares
+
+
+def np_update_plan(ps, mm, gc, spd, v, Rz, R, pos, vd, **over):
+    """update_plan (S/A1RobotControl.cpp:148-202) restated in plain numpy for n robots at a parameter set, one rounding per operation in the reference's order:
+    -> (gait_counter, plan_contacts, foot_pos_target_rel, _abs, _world).  What holds the oracle where the reference's own constants cannot be moved (the two
+    FOOT_DELTA_*_LIMITs, gait_counter_reset); over: single fields of the set replaced"""
+    ps = dict(ps, **over)
+    n = len(mm); walk = np.asarray(mm).astype(bool)[:, None]
+    g = np.where(walk, np.fmod(gc + spd, ps["counter_per_gait"]), np.asarray(ps["gait_counter_reset"], dtype=np.float64))
+    pc = np.where(walk, g <= ps["counter_per_swing"], True).astype(np.uint8)
+    dfp = np.asarray(ps["default_foot_pos"], dtype=np.float64)
+    vrx = Rz[:, 0] * v[:, 0] + Rz[:, 3] * v[:, 1] + Rz[:, 6] * v[:, 2]; vry = Rz[:, 1] * v[:, 0] + Rz[:, 4] * v[:, 1] + Rz[:, 7] * v[:, 2]
+    k = np.sqrt(np.abs(dfp[2]) / 9.8)                                  # default_foot_pos(2): the z of leg 0, for every leg
+    half = ((ps["counter_per_swing"] / spd) * ps["gait_dt"]) / 2.0    # (n, 4)
+    dx = k * (vrx - vd[:, 0])[:, None] + half * vd[:, 0:1]; dy = k * (vry - vd[:, 1])[:, None] + half * vd[:, 1:2]
+    dx = np.clip(dx, -ps["foot_delta_x_limit"], ps["foot_delta_x_limit"]); dy = np.clip(dy, -ps["foot_delta_y_limit"], ps["foot_delta_y_limit"])
+    rel = np.tile(dfp, (n, 1)).reshape(n, 4, 3).copy(); rel[:, :, 0] += dx; rel[:, :, 1] += dy
+    ab = np.stack([R[:, 3 * r, None] * rel[:, :, 0] + R[:, 3 * r + 1, None] * rel[:, :, 1] + R[:, 3 * r + 2, None] * rel[:, :, 2] for r in range(3)], axis=2)
+    wo = ab + pos[:, None, :]
+    return g, pc, rel.reshape(n, 12), ab.reshape(n, 12), wo.reshape(n, 12)
+
+
+def np_contacts(gc, plan, ff, early_prev, contact_per_swing, foot_force_low):
+    """the early-contact lines (S/A1RobotControl.cpp:259-271) in plain numpy: -> (contacts, early_contacts)"""
+    early = np.where(gc <= contact_per_swing * 1.5, False, np.asarray(early_prev, dtype=bool))
+    early = early | ((plan == 0) & (gc > contact_per_swing * 1.5) & (ff > foot_force_low))
+    return ((plan != 0) | early).astype(np.uint8), early
+
+
+def plan_inputs(scen, rng, n, ps):
+    """random attitude / velocities for update_plan; the commanded velocities of robots 0 .. 7 are +-3 m/s in x or y (both limits saturate on both sides, asserted by the
+    caller on the yardstick), every ninth robot is commanded nothing"""
+    yaw = rng.uniform(-np.pi, np.pi, n); R = scen.rot_zyx(rng.uniform(-0.2, 0.2, n), rng.uniform(-0.2, 0.2, n), yaw).reshape(n, 9); Rz = scen.rot_zyx(0 * yaw, 0 * yaw, yaw).reshape(n, 9)
+    v = rng.normal(0, 0.3, (n, 3)); vd = np.c_[rng.normal(0, 0.3, (n, 2)), np.zeros(n)]; pos = rng.normal(0, 2.0, (n, 3))
+    for b, (ax, sg) in enumerate([(0, 1), (0, -1), (1, 1), (1, -1)] * 2):
+        if b < n:
+            vd[b, :2] = 0.0; vd[b, ax] = 3.0 * sg
+    vd[8::9] = 0.0
+    return dict(v=v, Rz=Rz, R=R, pos=pos, vd=vd)

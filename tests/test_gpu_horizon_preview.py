@@ -27,12 +27,12 @@ def _gait_inputs(rng, n, h, tps):
     return mm, gc, spd
 
 
-def _oracle_plan_forward(oracle, mm, gc, spd, h, tps):
+def _oracle_plan_forward(oracle, mm, gc, spd, h, tps, gp=None):
     """plan_contacts of the next (h - 1) * tps calls of the oracle's update_plan (orc_update_plan, the restatement oracle/_ref pins to the reference's sources) at constant
     speed, every tps-th one kept: (n, h - 1, 4).  One C call per robot and tick, on the robot's own words of the arrays below (the Python wrapper oracle.update_plan
-    makes the same call; it allocates nine arrays per call, which 4.6 M calls cannot afford)."""
+    makes the same call; it allocates nine arrays per call, which 4.6 M calls cannot afford).  gp: oracle.gait_params of another gait (default: the reference's)."""
     n = len(mm)
-    gp = oracle.gait_params(DEFAULT_FOOT_POS)
+    gp = oracle.gait_params(DEFAULT_FOOT_POS) if gp is None else gp
     fn = oracle.lib().orc_update_plan
     g = np.array(gc, dtype=np.float64); s = np.ascontiguousarray(spd, dtype=np.float64)
     z3 = np.zeros(3); eye = np.eye(3).reshape(9).copy(); pc = np.zeros(4, np.uint8); rel = np.zeros(12); ab = np.zeros(12); wo = np.zeros(12)

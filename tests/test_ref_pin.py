@@ -359,3 +359,160 @@ def test_update_path_reinitialises_when_the_hessian_pattern_changes(oracle, scen
     assert seen == [0, 0, 1, 0, 0, 1, 0, 1, 1], seen
     level = {n_ for n_, y_ in zip(nnzs, yaws) if y_ == 0.0}; yawed = {n_ for n_, y_ in zip(nnzs, yaws) if y_ != 0.0}
     assert len(level) == 1 and len(yawed) == 1 and max(level) < min(yawed) <= 120 * 121 // 2, (nnzs,)   # the level state has exact zeros in P, the pitched one none
+
+
+# ------------------------------------------------------------------------------------------------ the caller-side rows at other parameters
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_caller_side_rows_equal_reference_at_other_parameters(oracle, scen, name):
+    """update_plan, generate_swing_legs_ctrl and compute_joint_torques of the reference at gpu_common.PARAM_SETS (other period, swing length, control_dt, default_foot_pos
+    with four heights, kp / kd / km; the swing legs' dt differs from the plan's control_dt) against the oracle over one full cycle of the slowest leg, per-leg speeds
+    2 / 2.5 / 5 / 10, at the bars of test_caller_side_tick_chain_equals_reference: element-wise rows bit for bit, 1e-15 on foot_pos_target_last_time, the foot force within
+    1e-9 scaled by the gains (gpu_common.force_bar).  The contact rows come from a second controller whose counter_per_swing is the CONTACT config's (set A: 100 beside the
+    gait's 120; the reference has one field for both), fed the first one's counters and planned contacts.
+    FOOT_FORCE_LOW and FOOT_DELTA_*_LIMIT are compile-time constants of the reference (30, 0.1): the oracle runs at those values on this side, and is held at 45 and
+    0.06 / 0.14 -- and at the set's gait_counter_reset, which the reference hard-codes too -- to the plain numpy restatement of those lines (gpu_common.np_update_plan /
+    np_contacts) on the same inputs, bit for bit."""
+    import gpu_common as G
+    ps = G.PARAM_SETS[name]
+    rng = np.random.default_rng(1700 + ord(name))
+    ticks = int(ps["counter_per_gait"] / min(G.PARAM_SPEEDS))
+    dfp = np.asarray(ps["default_foot_pos"]); spd = np.array(G.PARAM_SPEEDS); dt = ps["control_dt"]
+    c = REF.Controller(); c2 = REF.Controller()
+    for k in (c, c2):
+        k.set("use_terrain_adapt", [1]); k.set("movement_mode", [1]); k.set("default_foot_pos", dfp)
+        k.set("counter_per_gait", [ps["counter_per_gait"]]); k.set("control_dt", [ps["gait_dt"]])
+        k.set("kp_foot", np.tile(ps["kp_foot"], 4)); k.set("kd_foot", np.tile(ps["kd_foot"], 4)); k.set("km_foot", ps["km_foot"])
+    c.set("counter_per_swing", [ps["counter_per_swing"]]); c2.set("counter_per_swing", [ps["contact_per_swing"]])
+    gp_ref = G.oracle_gait(oracle, ps, dx=0.1, dy=0.1, reset=(0.0, 120.0, 120.0, 0.0))   # the reference's compile-time limits
+    gp_set = G.oracle_gait(oracle, ps)
+    cs_ref, cs_set = oracle.contact_state(), oracle.contact_state()
+    gc = np.array(ps["gait_counter_reset"]); early_np = np.zeros(4, bool)
+    st3 = [np.zeros(12) for _ in range(3)]
+    tau_prev = np.zeros(12); km = np.array(ps["km_foot"]); tg = np.array([0.8, 0, 0, -0.8, 0, 0, 0.8, 0, 0, -0.8, 0, 0])
+    worst = dict(target=0.0, kin=0.0); hits = {ps["counter_per_swing"]: 0, G.early_mark(ps): 0, 0.0: 0}; saturated = set(); early_n = 0; differ45 = 0
+    for t in range(ticks):
+        euler = np.array([rng.normal(0, 0.02), rng.normal(0, 0.02), 0.3 + 0.001 * t])
+        R = scen.rot_zyx(*euler); Rz = scen.rot_zyx(0.0, 0.0, euler[2])
+        pos = np.array([0.002 * t, 0.0, 0.3 + rng.normal(0, 0.005)]); v = np.array([0.3, 0, 0]) + rng.normal(0, 0.05, 3)
+        vd = np.array([[1.2, 0.4, 0.0], [-1.2, -0.4, 0.0], [0.1, 2.0, 0.0], [0.1, -2.0, 0.0], [0.2, 0.1, 0.0]][t % 5])   # saturates 0.06 / 0.14 / 0.1 on either side; the last is free
+        foot_abs = (R @ (dfp.reshape(4, 3) + rng.normal(0, 0.02, (4, 3))).T).T.reshape(12)
+        ff = rng.choice(G.force_values(ps), 4)
+        Jb = rng.normal(0, 0.2, (4, 9)); Jb[:, [0, 4, 8]] += 0.3
+        grf = rng.normal(0, 40, 12)
+        # ---- reference
+        c.set("gait_counter", gc); c.set("gait_counter_speed", spd)
+        c.set("root_lin_vel", v); c.set("root_lin_vel_d", vd); c.set("root_pos", pos); c.set_mat("root_rot_mat", R); c.set_mat("root_rot_mat_z", Rz)
+        c.set("foot_pos_abs", foot_abs); c.set("foot_force", ff)
+        J = np.zeros((12, 12))
+        for i in range(4):
+            J[3 * i:3 * i + 3, 3 * i:3 * i + 3] = Jb[i].reshape(3, 3).T
+        c.set_mat("j_foot", J); c.set("torques_gravity", tg)
+        c.update_plan(dt)
+        c.generate_swing_legs_ctrl(dt)
+        gc_r = c.get("gait_counter", 4); plan_r = c.get("plan_contacts", 4)
+        c2.set("gait_counter", gc_r); c2.set("plan_contacts", plan_r); c2.set("foot_force", ff); c2.set("foot_pos_abs", foot_abs); c2.set_mat("root_rot_mat_z", Rz)
+        c2.generate_swing_legs_ctrl(dt)
+        ct_r = c2.get("contacts", 4).astype(np.uint8)
+        c.set("contacts", ct_r); c.set("foot_forces_grf", grf)
+        c.compute_joint_torques()
+        # ---- oracle, at the reference's compile-time constants
+        gc_o, plan, rel, ab, wo = oracle.update_plan(gp_ref, 1, gc, spd, v, Rz.reshape(9), R.reshape(9), pos, vd)
+        assert np.array_equal(gc_o, gc_r) and np.array_equal(plan, plan_r.astype(np.uint8)), t
+        assert np.array_equal(rel, c.get("foot_pos_target_rel", 12)) and np.array_equal(ab, c.get("foot_pos_target_abs", 12)) and np.array_equal(wo, c.get("foot_pos_target_world", 12)), t
+        cur, kin = oracle.swing_legs(Rz.reshape(9), foot_abs, gc_o, rel, st3[0], st3[1], st3[2], kp=ps["kp_foot"], kd=ps["kd_foot"], counter_per_swing=ps["counter_per_swing"], dt=dt)
+        assert np.array_equal(cur, c.get("foot_pos_cur", 12)) and np.array_equal(st3[0], c.get("foot_pos_start", 12)), t
+        d_t, d_k = np.abs(st3[2] - c.get("foot_pos_target_last_time", 12)).max(), np.abs(kin - c.get("foot_forces_kin", 12)).max()
+        worst["target"] = max(worst["target"], d_t); worst["kin"] = max(worst["kin"], d_k)
+        assert d_t <= 1e-15 and d_k <= G.force_bar(ps), (t, d_t, d_k)
+        st3[2] = c.get("foot_pos_target_last_time", 12).copy(); kin = c.get("foot_forces_kin", 12).copy()
+        ct, rec, _, _ = oracle.contact_terrain_step(cs_ref, gc_o, plan, ff, foot_abs, pos[2], 0.0, counter_per_swing=ps["contact_per_swing"], foot_force_low=30.0)
+        assert np.array_equal(ct, ct_r) and np.array_equal(rec, c2.get("foot_pos_recent_contact", 12)), t
+        tau = oracle.joint_torques(1 if t >= 9 else 0, ct, Jb.reshape(36), grf, kin, km, tg, tau_prev)
+        assert np.array_equal(tau, c.get("joint_torques", 12)), (t, tau - c.get("joint_torques", 12))
+        # ---- oracle at the set's own limits, reset and force threshold, against plain numpy
+        one = lambda a: np.asarray(a)[None]
+        for mode in (1, 0):
+            o5 = oracle.update_plan(gp_set, mode, gc, spd, v, Rz.reshape(9), R.reshape(9), pos, vd)
+            n5 = G.np_update_plan(ps, np.array([mode]), one(gc), one(spd), one(v), one(Rz.reshape(9)), one(R.reshape(9)), one(pos), one(vd))
+            for a, b in zip(o5, n5):
+                assert np.array_equal(a, b[0]), (t, mode)
+            if mode == 1:
+                d = o5[2].reshape(4, 3)[:, :2] - dfp.reshape(4, 3)[:, :2]
+                for ax, lim in ((0, ps["foot_delta_x_limit"]), (1, ps["foot_delta_y_limit"])):
+                    saturated |= {(ax, s) for s in (1, -1) if np.any(np.abs(d[:, ax] - s * lim) <= 1e-16)}
+        ct45, _, _, _ = oracle.contact_terrain_step(cs_set, gc_o, plan, ff, foot_abs, pos[2], 0.0, counter_per_swing=ps["contact_per_swing"], foot_force_low=ps["foot_force_low"])
+        ct_np, early_np = G.np_contacts(gc_o, plan, ff, early_np, ps["contact_per_swing"], ps["foot_force_low"])
+        assert np.array_equal(ct45, ct_np), t
+        differ45 += int((ct45 != ct).sum()); early_n += int(((ct45 == 1) & (plan == 0)).sum())
+        for x in hits:
+            hits[x] += int((gc_o == x).sum())
+        tau_prev = tau; gc = gc_o
+    print(f"set {name}: {ticks} ticks, worst |d foot_pos_target_last_time| {worst['target']:.1e}, |d foot_forces_kin| {worst['kin']:.1e} N (bar {G.force_bar(ps):.2e}); counter hits {hits}, "
+          f"{early_n} early contacts at 45 N, {differ45} contacts differ between 30 N and 45 N")
+    assert min(hits.values()) >= 4, hits            # every leg has been exactly on the lift-off mark, the early-contact mark and the wrap
+    assert saturated == {(0, 1), (0, -1), (1, 1), (1, -1)}, saturated
+    assert early_n > 0 and differ45 > 0
+    c.close(); c2.close()
+
+
+@pytest.mark.parametrize("flat,dt", [(0, 0.002), (0, 0.005), (0, 0.0025), (1, 0.005)])
+def test_ekf_equals_reference_without_flat_ground_and_at_other_dt(oracle, scen, flat, dt):
+    """A1BasicEKF(assume_flat_ground = false) and dt = 0.002 / 0.005 (the control_dt of gpu_common.PARAM_SETS), 200 ticks: orc_ekf_step within the 1e-9 of
+    test_ekf_equals_reference, the device variant within 1e-10 of the pinned one (the bar tests/test_gpu_caller_side.py::test_ekf_N4c_sequence holds the kernel to).
+    On the oracle alone, one parameter at a time: the run differs from the one with assume_flat_ground put back to 1, and from the one with dt put back to 0.0025, or the
+    comparison could not see that parameter."""
+    rng = np.random.default_rng(151)
+    c = REF.Controller(); c.ekf_new(bool(flat))
+    state, dev = oracle.ekf_state(), oracle.ekf_state()
+    back = {k: v for k, v in dict(assume_flat_ground=(1, dt), dt=(flat, 0.0025)).items() if v != (flat, dt)}     # one parameter back at its default each
+    back_state = {k: oracle.ekf_state() for k in back}; moved = {k: 0.0 for k in back}
+    base = np.array([0.18, 0.13, -0.3, 0.18, -0.13, -0.3, -0.18, 0.13, -0.3, -0.18, -0.13, -0.3])
+    worst = worst_dev = 0.0
+    for t in range(200):
+        mm = 1 if (t > 3 and rng.random() < 0.8) else 0
+        yaw = rng.uniform(-3, 3); e = rng.normal(0, 0.05, 2); R = scen.rot_zyx(e[0], e[1], yaw)
+        fk = base + rng.normal(0, 0.01, 12); fv = rng.normal(0, 0.3, 12); acc = np.array([0, 0, 9.81]) + rng.normal(0, 0.3, 3)
+        w = rng.normal(0, 0.3, 3); ff = rng.uniform(0, 160, 4)
+        c.set("movement_mode", [mm]); c.set("foot_force", ff); c.set_mat("root_rot_mat", R); c.set("imu_acc", acc); c.set("imu_ang_vel", w)
+        c.set("foot_pos_rel", fk); c.set("foot_vel_rel", fv)
+        if t == 0:
+            c.ekf_init_state()
+        else:
+            c.ekf_update(dt)
+        p_o, v_o, e_o = oracle.ekf_step(state, dt, mm, ff, R.reshape(9), acc, w, fk, fv, assume_flat_ground=flat)
+        p_d, v_d, e_d = oracle.ekf_step(dev, dt, mm, ff, R.reshape(9), acc, w, fk, fv, assume_flat_ground=flat, device=True)
+        p_b = {k: oracle.ekf_step(back_state[k], v[1], mm, ff, R.reshape(9), acc, w, fk, fv, assume_flat_ground=v[0])[:2] for k, v in back.items()}
+        if t > 0:
+            worst = max(worst, np.abs(p_o - c.get("estimated_root_pos", 3)).max(), np.abs(v_o - c.get("estimated_root_vel", 3)).max())
+            worst_dev = max(worst_dev, np.abs(p_o - p_d).max(), np.abs(v_o - v_d).max())
+            for k, (pb, vb) in p_b.items():
+                moved[k] = max(moved[k], np.abs(p_o - pb).max(), np.abs(v_o - vb).max())
+            assert np.array_equal(e_o, c.get("estimated_contacts", 4).astype(np.uint8)) and np.array_equal(e_d, e_o), t
+    print(f"EKF flat {flat} dt {dt}: oracle vs reference {worst:.1e}, device variant vs pinned {worst_dev:.1e}; with one parameter back at its default the run lies "
+          + ", ".join(f"{k} {v:.1e}" for k, v in moved.items()) + " away")
+    assert moved and all(v > 1e-6 for v in moved.values()), moved
+    assert worst <= 1e-9 and worst_dev <= 1e-10, (worst, worst_dev)
+    c.close()
+
+
+def test_leg_kinematics_equals_reference_at_another_geometry(oracle):
+    """test_leg_kinematics_equals_reference at the leg geometry of gpu_common.PARAM_SET_A (every one of the five entries differs from leg to leg, thigh / calf near
+    0.25 / 0.27): that test's 2e-15 scaled by the ratio of the largest reach |ox| + |oy| + |d| + lt + lc to the A1's.  The A1's geometry gives another answer on every leg."""
+    import gpu_common as G
+    fix = np.asarray(G.PARAM_SET_A["rho_fix"])
+    assert all(len(set(np.abs(fix[:, j]).tolist())) == 4 for j in range(5))
+    rng = np.random.default_rng(12)
+    worst = 0.0; moved = np.full(4, np.inf)
+    for k in range(300):
+        q = rng.uniform(-1.5, 1.5, 12); qd = rng.normal(0, 3, 12); opt = rng.normal(0, 0.01, (4, 3))
+        R = np.eye(3).reshape(9)
+        o = oracle.leg_state(q, qd, R, np.zeros(3), np.zeros(3), rho_fix=fix, rho_opt=opt)
+        a1 = oracle.leg_state(q, qd, R, np.zeros(3), np.zeros(3), rho_opt=opt)
+        for leg in range(4):
+            p = REF.leg_fk(q[3 * leg:3 * leg + 3], opt[leg], fix[leg])
+            J = REF.leg_jac(q[3 * leg:3 * leg + 3], opt[leg], fix[leg])
+            worst = max(worst, np.abs(p - o["foot_pos_rel"][3 * leg:3 * leg + 3]).max(), np.abs(J - o["Jb"][9 * leg:9 * leg + 9]).max())
+            moved[leg] = min(moved[leg], np.abs(o["foot_pos_rel"][3 * leg:3 * leg + 3] - a1["foot_pos_rel"][3 * leg:3 * leg + 3]).max())
+    print(f"leg kinematics at set A's geometry: worst {worst:.1e} (bar {2e-15 * G.LEG_BAR_SCALE:.2e}); the A1's geometry lies at least {moved.min():.1e} away")
+    assert (moved > 1e-3).all(), moved
+    assert worst <= 2e-15 * G.LEG_BAR_SCALE, worst
