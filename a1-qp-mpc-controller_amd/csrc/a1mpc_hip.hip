@@ -607,6 +607,184 @@ __global__ __launch_bounds__(64) void a1mpc_horizon_states_kernel(const HorizonS
     }
 }
 
+// ---- single-rigid-body plant step (a1mpc_plant_step_batch): one control period of the nonlinear body under the forces of a solve -- semi-implicit Euler for the
+// translation, the Cayley map for the attitude (R brought back to orthogonal to first order at the start of a call), omega from the conserved world angular momentum
+// and the NEW attitude; the scheme is stated in include/a1mpc.h.
+// Memory- and launch-bound: 12 + 9 + 12 + 12 (+ 6) doubles and 4 bytes in, 12 + 9 + 12 doubles out per robot.
+//   lanes     the layout of a1mpc_horizon_states_kernel: one wavefront = one workgroup = 16 consecutive robots, lane = 4 * (robot of the wave) + l.  Lane l holds leg l's
+//             lever, force and contact byte (rotation, cross product and foot update need no exchange); the body state is carried by all four lanes of a robot.  The
+//             leg sums are x + shfl(lane ^ 1), then + shfl(lane ^ 2): (leg 0 + leg 1) + (leg 2 + leg 3) in every lane, IEEE addition being commutative.
+//   memory    the wave's robots own one contiguous run of every array.  Feet and forces are a lane's own 24 bytes of a 1536-byte run: read and written directly.  The
+//             state rows (12, 13 or 22 doubles), R and the wrench are shared by a robot's lanes: they pass through wave-private LDS in their memory layout, 64
+//             consecutive doubles per instruction.  Every global load is issued before the first operation; outputs may be the inputs (a wave loads all it reads before
+//             it stores, and no two waves share a robot).  Words [12, stride) of a state row are not stored.
+//   bits      contraction off and no fma: IEEE +, -, *, / alone, three-term sums left to right -- a pure function of the robot's own inputs, restated elementwise in
+//             tests/plant_ref.py.  The three inverse trigonometric calls at the end feed nothing.
+//   dead lanes (robots >= n of the last wave) load the wave's first robot, take part in every shuffle and store nothing, neither to LDS nor to memory.
+struct PlantArgs {
+    int32_t n, stride, substeps;
+    double dt, gravity, mass, inertia[9];
+    const double *state, *R, *foot, *grf, *ext;   // ext may be null
+    const uint8_t* contacts;
+    double *state_out, *R_out, *foot_out;
+};
+constexpr int kPlState = 16 * 22, kPlR = 16 * 9, kPlExt = 16 * 6;
+__device__ __forceinline__ double pl_pick(int l, double a0, double a1, double a2, double a3) { return l == 0 ? a0 : (l == 1 ? a1 : (l == 2 ? a2 : a3)); }
+__device__ __forceinline__ double pl_legs(double x) { const double p = x + __shfl_xor(x, 1, 64); return p + __shfl_xor(p, 2, 64); }
+// y = M x and y = M^T x of a row-major 3 x 3, each sum left to right
+#define A1_PL_MV(y, M, x) do { _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_) y[i_] = (M[3 * i_] * x[0] + M[3 * i_ + 1] * x[1]) + M[3 * i_ + 2] * x[2]; } while (0)
+#define A1_PL_MTV(y, M, x) do { _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_) y[i_] = (M[i_] * x[0] + M[3 + i_] * x[1]) + M[6 + i_] * x[2]; } while (0)
+__global__ __launch_bounds__(64) void a1mpc_plant_step_kernel(const PlantArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double plds[kPlState + kPlR + kPlExt];
+    double* const S = plds; double* const RL = plds + kPlState; double* const E = plds + kPlState + kPlR;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, stride = a.stride;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    // every load, then the LDS writes: element e of the wave's run of an array sits at e in LDS.  Past the run: the run's first word again, no branch around the load
+    const int cs = live * stride, cr = live * 9, ce = a.ext ? live * 6 : 0;
+    const double *gs = a.state + first * stride, *gr = a.R + first * 9, *ge = a.ext ? a.ext + first * 6 : a.R;
+    double vs[6], vr[3], ve[2];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; vs[m] = gs[e < cs ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vr[m] = gr[e < cr ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; ve[m] = ge[e < ce ? e : 0]; }
+    double r[3], f[3];
+    {
+        const double *fp = a.foot + b * 12 + 3 * l, *gp = a.grf + b * 12 + 3 * l;
+        r[0] = fp[0]; r[1] = fp[1]; r[2] = fp[2]; f[0] = gp[0]; f[1] = gp[1]; f[2] = gp[2];
+    }
+    const bool stance = a.contacts[b * 4 + l] != 0;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; if (e < cs) S[e] = vs[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cr) RL[e] = vr[m]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; if (e < ce) E[e] = ve[m]; }
+    WaveStage::sync();
+    double pos[3], w[3], v[3], R[9], fe[3] = {0.0, 0.0, 0.0}, te[3] = {0.0, 0.0, 0.0};
+    {
+        const double* x = S + q * stride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pos[k] = x[3 + k]; w[k] = x[6 + k]; v[k] = x[9 + k]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = RL[q * 9 + k];
+    }
+    const bool with_ext = a.ext != nullptr;
+    if (with_ext) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { fe[k] = E[q * 6 + k]; te[k] = E[q * 6 + 3 + k]; }
+    }
+    // once: R <- R - R (R^T R - I) / 2, the first-order step to the nearest orthogonal matrix (the rounding of earlier calls' products does not pile up in R^T R,
+    // through which L is rebuilt below); I_b^-1 by cofactors; L = R (I_b (R^T omega)); h = dt / substeps
+    {
+        double E[9], Rp[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) E[3 * i + j] = (R[i] * R[j] + R[3 + i] * R[3 + j]) + R[6 + i] * R[6 + j];
+        E[0] = E[0] - 1.0; E[4] = E[4] - 1.0; E[8] = E[8] - 1.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Rp[3 * i + j] = R[3 * i + j] - 0.5 * ((R[3 * i] * E[j] + R[3 * i + 1] * E[3 + j]) + R[3 * i + 2] * E[6 + j]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rp[k];
+    }
+    double Ii[9], L[3];
+    {
+        const double* I = a.inertia;
+        const double c00 = I[4] * I[8] - I[5] * I[7], c01 = I[5] * I[6] - I[3] * I[8], c02 = I[3] * I[7] - I[4] * I[6];
+        const double id = 1.0 / ((I[0] * c00 + I[1] * c01) + I[2] * c02);
+        Ii[0] = c00 * id; Ii[1] = (I[2] * I[7] - I[1] * I[8]) * id; Ii[2] = (I[1] * I[5] - I[2] * I[4]) * id;
+        Ii[3] = c01 * id; Ii[4] = (I[0] * I[8] - I[2] * I[6]) * id; Ii[5] = (I[2] * I[3] - I[0] * I[5]) * id;
+        Ii[6] = c02 * id; Ii[7] = (I[1] * I[6] - I[0] * I[7]) * id; Ii[8] = (I[0] * I[4] - I[1] * I[3]) * id;
+        double wb[3], Iw[3];
+        A1_PL_MTV(wb, R, w); A1_PL_MV(Iw, I, wb); A1_PL_MV(L, R, Iw);
+    }
+    const double h = a.dt / static_cast<double>(a.substeps), half = h / 2.0, m = a.mass, g = a.gravity;
+    for (int step = 0; step < a.substeps; ++step) {
+        // 1, 2: this leg's world force (a swing leg: +0, selected) and torque, summed over the legs
+        double fw[3], F[3], T[3];
+        A1_PL_MV(fw, R, f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fw[k] = stance ? fw[k] : 0.0;
+        const double tq[3] = {r[1] * fw[2] - r[2] * fw[1], r[2] * fw[0] - r[0] * fw[2], r[0] * fw[1] - r[1] * fw[0]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            F[k] = pl_legs(fw[k]); T[k] = pl_legs(tq[k]);
+            if (with_ext) { F[k] = F[k] + fe[k]; T[k] = T[k] + te[k]; }
+        }
+        // 3: semi-implicit Euler
+        double dp[3];
+        v[0] = v[0] + h * (F[0] / m); v[1] = v[1] + h * (F[1] / m); v[2] = v[2] + h * (F[2] / m + g);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { dp[k] = h * v[k]; pos[k] = pos[k] + dp[k]; }
+        // 4: R' = cay((h / 2) omega) R
+        double Rn[9];
+        {
+            const double a0 = half * w[0], a1 = half * w[1], a2 = half * w[2];
+            const double s = 2.0 / (1.0 + ((a0 * a0 + a1 * a1) + a2 * a2));
+            const double Cm[9] = {1.0 - s * (a1 * a1 + a2 * a2), s * (a0 * a1 - a2), s * (a0 * a2 + a1),
+                                  s * (a0 * a1 + a2), 1.0 - s * (a0 * a0 + a2 * a2), s * (a1 * a2 - a0),
+                                  s * (a0 * a2 - a1), s * (a1 * a2 + a0), 1.0 - s * (a0 * a0 + a1 * a1)};
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Cm[3 * i] * R[j] + Cm[3 * i + 1] * R[3 + j]) + Cm[3 * i + 2] * R[6 + j];
+        }
+        // 5: L' = L + h tau, omega' = R' (I_b^-1 (R'^T L'))
+        {
+            double Lb[3], wb[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) L[k] = L[k] + h * T[k];
+            A1_PL_MTV(Lb, Rn, L); A1_PL_MV(wb, Ii, Lb); A1_PL_MV(w, Rn, wb);
+        }
+        // 6: a stance foot stays where it is in the world, a swing foot where it is in the body
+        {
+            double rb[3], rs[3];
+            A1_PL_MTV(rb, R, r); A1_PL_MV(rs, Rn, rb);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) r[k] = stance ? r[k] - dp[k] : rs[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    }
+    // the angles of rot_zyx, read off R (an output only)
+    const double sp = -R[6], spc = sp > 1.0 ? 1.0 : (sp < -1.0 ? -1.0 : sp);   // (a NaN stays a NaN)
+    const double roll = atan2(R[7], R[8]), pitch = asin(spc), yaw = atan2(R[3], R[0]);
+    // out: lane l puts state triple l (0 euler, 1 pos, 2 omega, 3 v) and, l < 3, row l of R into the LDS images; the images go out as they came in
+    WaveStage::sync();   // (every lane has read its inputs)
+    if (alive) {
+        double* x = S + q * stride + 3 * l;
+        x[0] = pl_pick(l, roll, pos[0], w[0], v[0]); x[1] = pl_pick(l, pitch, pos[1], w[1], v[1]); x[2] = pl_pick(l, yaw, pos[2], w[2], v[2]);
+        if (l < 3) {
+            double* o = RL + q * 9 + 3 * l;
+            o[0] = pl_pick(l, R[0], R[3], R[6], 0.0); o[1] = pl_pick(l, R[1], R[4], R[7], 0.0); o[2] = pl_pick(l, R[2], R[5], R[8], 0.0);
+        }
+        double* fo = a.foot_out + b * 12 + 3 * l;
+        fo[0] = r[0]; fo[1] = r[1]; fo[2] = r[2];
+    }
+    WaveStage::sync();
+    double *os = a.state_out + first * stride, *orr = a.R_out + first * 9;
+#pragma unroll
+    for (int mm = 0; mm < 6; ++mm) {
+        const int e = lane + 64 * mm;
+        const int col = stride == 12 ? e % 12 : (stride == 13 ? e % 13 : e % 22);
+        if (e < cs && col < 12) os[e] = S[e];
+    }
+#pragma unroll
+    for (int mm = 0; mm < 3; ++mm) { const int e = lane + 64 * mm; if (e < cr) orr[e] = RL[e]; }
+}
+#undef A1_PL_MV
+#undef A1_PL_MTV
+
 thread_local std::string g_last_error;
 std::mutex g_cache_mu;
 thread_local bool g_clk_ran = false;
@@ -3184,6 +3362,74 @@ a1mpc_status a1mpc_horizon_states_batch(a1mpc_handle h, int32_t n, const double*
 a1mpc_status a1mpc_horizon_states_ticks_batch(a1mpc_handle h, int32_t n, const double* tick, const double* R_world, const double* foot_abs, int32_t foot_stride,
                                               const double* yaw_A, const double* u_full, double* x_pred_out, double* cost_out) {
     return horizon_states_host_impl(h, n, true, tick, nullptr, R_world, foot_abs, foot_stride, yaw_A, u_full, x_pred_out, cost_out);
+}
+// ---- the plant step behind the C ABI: a1mpc_plant_step_kernel, no handle state
+void a1mpc_default_plant_config(a1mpc_plant_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof *c);
+    c->dt = 0.0025; c->substeps = 1; c->gravity_z = -9.8;
+}
+// what the two entries refuse, or null (all before the first HIP call)
+static const char* invalid_plant_step(a1mpc_handle h, const a1mpc_plant_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                      const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* state_out, const double* R_world_out,
+                                      const double* foot_abs_out) {
+    if (!h) return "null handle";
+    if (!cfg) return "null a1mpc_plant_config";
+    if (cfg->substeps < 1 || cfg->substeps > 64) return "a1mpc_plant_config.substeps outside 1 .. 64";
+    if (!(cfg->dt > 0.0) || !std::isfinite(cfg->dt)) return "a1mpc_plant_config.dt must be positive and finite";
+    if (!std::isfinite(cfg->gravity_z)) return "a1mpc_plant_config.gravity_z must be finite";
+    if (state_stride != 12 && state_stride != 13 && state_stride != 22) return "state_stride must be 12, 13 or 22";
+    if (n < 0) return "negative n";
+    if (n > h->max_batch) return "n > max_batch given to a1mpc_create";
+    if (!state_in) return "null state_in";
+    if (!R_world) return "null R_world";
+    if (!foot_abs) return "null foot_abs";
+    if (!grf_body) return "null grf_body";
+    if (!contacts) return "null contacts";
+    if (!state_out) return "null state_out";
+    if (!R_world_out) return "null R_world_out";
+    if (!foot_abs_out) return "null foot_abs_out";
+    return nullptr;
+}
+// the launch alone: device pointers, validated by the caller, which also orders and marks the stream.  One wavefront per workgroup, 16 robots each
+static void launch_plant_step(a1mpc_handle h, const a1mpc_plant_config& cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                              const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, double* state_out, double* R_world_out,
+                              double* foot_abs_out, hipStream_t s) {
+    PlantArgs a;
+    a.n = n; a.stride = state_stride; a.substeps = cfg.substeps; a.dt = cfg.dt; a.gravity = cfg.gravity_z; a.mass = h->cfg.mass;
+    for (int i = 0; i < 9; ++i) a.inertia[i] = h->cfg.inertia_body[i];
+    a.state = state_in; a.R = R_world; a.foot = foot_abs; a.grf = grf_body; a.ext = ext_wrench; a.contacts = contacts;
+    a.state_out = state_out; a.R_out = R_world_out; a.foot_out = foot_abs_out;
+    hipLaunchKernelGGL(a1mpc_plant_step_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, a);
+}
+a1mpc_status a1mpc_plant_step_batch_device(a1mpc_handle h, const a1mpc_plant_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                           const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                           const double* d_ext_wrench, double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, void* hip_stream) {
+    if (const char* bad = invalid_plant_step(h, cfg, n, d_state_in, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_state_out, d_R_world_out, d_foot_abs_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_plant_step(h, *cfg, n, d_state_in, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_ext_wrench, d_state_out, d_R_world_out,
+                                      d_foot_abs_out, s));
+    return A1MPC_OK;
+}
+// the host-pointer entry: every array through Staging.  The device step runs IN PLACE on the staged inputs; where a state row is wider than the 12 words the kernel
+// writes and state_out is another array than state_in, state_out's own rows are staged in as well, so that the words the step does not write go back as they came
+a1mpc_status a1mpc_plant_step_batch(a1mpc_handle h, const a1mpc_plant_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                    const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, double* state_out,
+                                    double* R_world_out, double* foot_abs_out) {
+    if (const char* bad = invalid_plant_step(h, cfg, n, state_in, state_stride, R_world, foot_abs, grf_body, contacts, state_out, R_world_out, foot_abs_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const size_t W = static_cast<size_t>(state_stride);
+    double *d_state = sg.in(state_in, W), *d_R = sg.in(R_world, 9), *d_foot = sg.in(foot_abs, 12);
+    const double *d_grf = sg.in(grf_body, 12), *d_ext = ext_wrench ? sg.in(ext_wrench, 6) : nullptr;
+    const uint8_t* d_ct = sg.in(contacts, 4);
+    double* d_out = (W == 12 || state_out == state_in) ? d_state : sg.in(static_cast<const double*>(state_out), W);
+    sg.back(state_out, d_out, W); sg.back(R_world_out, d_R, 9); sg.back(foot_abs_out, d_foot, 12);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_plant_step(h, *cfg, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_out, d_R, d_foot, s));
+    return sg.finish();
 }
 #undef A1_STAGE_BEGIN
 #undef A1_STAGE_DEVICE

@@ -66,6 +66,10 @@ class CommandConfig(C.Structure):  # a1mpc_command_config: the constants of main
                 ("lock_speed", C.c_double), ("mpc_init_ticks", C.c_int32)]
 
 
+class PlantConfig(C.Structure):  # a1mpc_plant_config: one call of the single-rigid-body plant advances by dt in `substeps` sub-steps
+    _fields_ = [("dt", C.c_double), ("substeps", C.c_int32), ("gravity_z", C.c_double)]
+
+
 TICK_SENSOR_POINTERS = ("quat", "imu_acc_raw", "imu_gyro_raw", "cmd", "mode_toggle", "body_height", "ctrl_state", "root_pos_d", "kp_linear_xy", "mpc_init_counter")
 COMMAND_STATE_FIELDS = ("body_height", "ctrl_state", "root_euler_d", "root_pos_d", "kp_linear_xy", "mpc_init_counter")   # carried by the caller, in the C ABI's order
 
@@ -85,7 +89,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
+EXPORTS = ["a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
+           "a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
            "a1mpc_command_batch", "a1mpc_command_batch_device", "a1mpc_control_tick_sensors_device", "a1mpc_balance_wrench_kp_batch", "a1mpc_balance_wrench_kp_batch_device",
            "a1mpc_default_balance_gains", "a1mpc_balance_wrench_batch", "a1mpc_balance_wrench_batch_device", "a1mpc_balance_solve_batch_device", "a1mpc_contacts_batch",
            "a1mpc_contacts_batch_device", "a1mpc_control_tick_balance_device",
@@ -212,6 +217,10 @@ def load_library(path=None):
         lib.a1mpc_horizon_states_batch_device.argtypes = [vp, i32] + [vpp] * 4 + [i32] + [vpp] * 4 + [vpp]; lib.a1mpc_horizon_states_batch_device.restype = C.c_int
         lib.a1mpc_horizon_states_ticks_batch.argtypes = [vp, i32, dp, dp, dp, i32, dp, dp, dp, dp]; lib.a1mpc_horizon_states_ticks_batch.restype = C.c_int
         lib.a1mpc_horizon_states_ticks_batch_device.argtypes = [vp, i32] + [vpp] * 3 + [i32] + [vpp] * 4 + [vpp]; lib.a1mpc_horizon_states_ticks_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_plant_step_batch"):   # (the single-rigid-body plant step; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_default_plant_config.argtypes = [C.POINTER(PlantConfig)]; lib.a1mpc_default_plant_config.restype = None
+        lib.a1mpc_plant_step_batch.argtypes = [vp, C.POINTER(PlantConfig), i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, dp]; lib.a1mpc_plant_step_batch.restype = C.c_int
+        lib.a1mpc_plant_step_batch_device.argtypes = [vp, C.POINTER(PlantConfig), i32, vpp, i32] + [vpp] * 8 + [vpp]; lib.a1mpc_plant_step_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -496,6 +505,42 @@ class Engine:
         rc = self.lib.a1mpc_horizon_states_ticks_batch_device(self._h, int(n), ptr(d_tick), ptr(d_R), ptr(d_foot), int(foot_stride), ptr(d_yaw_A), ptr(d_u),
                                                               ptr(d_x_pred), ptr(d_cost), C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_horizon_states_ticks_batch_device")
+
+    # ---- what a robot does with the solved forces: one control period of the nonlinear single rigid body (the plant that closes the loop on the device) ----
+    def plant_config(self, **fields):
+        """a1mpc_default_plant_config ({0.0025, 1, -9.8}) with `fields` (dt, substeps, gravity_z) overridden"""
+        pc = PlantConfig(); self.lib.a1mpc_default_plant_config(C.byref(pc))
+        for k, v in fields.items():
+            if not hasattr(pc, k):
+                raise KeyError(k)
+            setattr(pc, k, int(v) if k == "substeps" else float(v))
+        return pc
+
+    def plant_step(self, state, R, foot, grf, contacts, ext_wrench=None, plant=None):
+        """dict(state (n, stride): [euler, pos, omega, v] stepped, words [12:stride) as they came; R (n, 9); foot (n, 12)): a1mpc_plant_step_batch.  state (n, 12 | 13 | 22)
+        rows of [euler (not read), pos, omega (world), v], R body -> world, foot = foot_pos_abs, grf = the BODY-frame grf of a solve, ext_wrench (n, 6) world frame or None"""
+        pc = self.plant_config() if plant is None else plant
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6))
+        state_out = state.copy(); R_out = np.zeros((n, 9)); foot_out = np.zeros((n, 12))
+        rc = self.lib.a1mpc_plant_step_batch(self._h, C.byref(pc), n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(state_out), _dp(R_out),
+                                             _dp(foot_out))
+        _check(self.lib, rc, "a1mpc_plant_step_batch")
+        return dict(state=state_out, R=R_out, foot=foot_out)
+
+    def plant_step_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_ext_wrench=None, d_state_out=None, d_R_out=None, d_foot_out=None, plant=None,
+                          stream=None):
+        """device pointers (torch tensors), asynchronous on `stream`: on the stream of the preceding solve_*_device it reads that solve's d_grf.  An output left None is
+        its input: the step runs in place"""
+        pc = self.plant_config() if plant is None else plant
+        out = lambda o, i: _dev(i if o is None else o)
+        rc = self.lib.a1mpc_plant_step_batch_device(self._h, C.byref(pc), int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf), _dev(d_contacts),
+                                                    _dev(d_ext_wrench), out(d_state_out, d_state), out(d_R_out, d_R), out(d_foot_out, d_foot),
+                                                    C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_plant_step_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

@@ -708,6 +708,55 @@ a1mpc_status a1mpc_horizon_states_ticks_batch_device(a1mpc_handle h, int32_t n, 
                                                      double* d_cost_out, void* hip_stream);
 
 /*
+ * The plant that closes the loop on the device: one control period of the NONLINEAR single rigid body under the forces a solve returned, n robots.  The reference gets
+ * its plant from a simulator or the robot; a1mpc_horizon_states_* is the MPC's own linear model (R_world and the yaw of A_c frozen, no gyroscopic term, feet that do not
+ * move with the body).  This is the body that model linearises:  a1mpc_solve_batch_ticks_device -> a1mpc_plant_step_batch_device -> a1mpc_solve_batch_ticks_device on one
+ * stream, in place on the tick records, R_world and the feet, with no host copy.
+ *   state      n x state_stride, state_stride = 12, 13 or 22: [0:3] euler  [3:6] pos  [6:9] omega (WORLD frame)  [9:12] v (world) -- the head of an x0 row (13) or of a
+ *              tick record (22).  The input euler is NOT read (the attitude state is R_world); words [12:state_stride) of state_out are never written: the gravity word
+ *              of an x0 row and the command half of a tick record survive a step in place
+ *   R_world    n x 9 row-major, body -> world        foot_abs  n x 12, leg l at [3l:3l+3]: the world-oriented lever from the COM (foot_pos_abs)
+ *   grf_body   n x 12 BODY-frame forces, grf_body_out of a solve        contacts  n x 4, non-zero = stance
+ *   ext_wrench NULL, or n x 6: [0:3] force, [3:6] torque about the COM, world frame
+ * mass and inertia_body are the handle's configuration; a1mpc_plant_config holds dt (one call advances by dt), substeps (1 .. 64) and gravity_z (default -9.8, the
+ * constant of mpc_states[12]).  Forces and contacts are held over the call.  Before the first sub-step:
+ *   0. R <- R - R (R^T R - I) / 2, the first-order step to the nearest orthogonal matrix.  L is carried INSIDE a call only (the handle keeps no state); the next call
+ *      rebuilds it from omega through R_world, and R^T R - I enters that rebuild times the condition number of the inertia.  Without this step the rounding of every
+ *      Cayley product so far piles up in R^T R (a random walk, 5e-15 after 400 calls) and the world angular momentum of a torque-free body moves by 2e-12 .. 4e-12
+ *      relative over 400 calls; with it R^T R - I stays at 4e-16 and the momentum within 8e-14.  An R_world that is orthogonal to rounding is changed by an ulp at most
+ *   then L = R (I_b (R^T omega)) and I_b^-1 by cofactors; then `substeps` times, with h = dt / substeps:
+ *   1. fw_l = R f_l for a stance leg, exactly +0 for a swing leg (selected, not multiplied: a NaN in a swing leg's force does not reach the body)
+ *   2. F = ((fw_0 + fw_1) + (fw_2 + fw_3)) + f_ext,  tau = ((r_0 x fw_0 + r_1 x fw_1) + (r_2 x fw_2 + r_3 x fw_3)) + tau_ext
+ *   3. v' = v + h (F / m + g e_z),  dp = h v',  pos' = pos + dp                                   (semi-implicit Euler)
+ *   4. a = (h / 2) omega,  R' = cay(a) R,  cay(a) = I + s ([a]x + [a]x^2),  s = 2 / (1 + a.a)     (the Cayley map: orthogonal in exact arithmetic, no sin / cos)
+ *   5. L' = L + h tau,  omega' = R' (I_b^-1 (R'^T L'))                                            (omega from the NEW attitude: L is kept to rounding over the call)
+ *   6. a stance foot is pinned in the world, r' = r - dp; a swing foot keeps its body-frame position, r' = R' (R^T r)
+ * After the last sub-step the angles are read off R in the rot_zyx convention: roll = atan2(R[7], R[8]), pitch = asin(clamp(-R[6], -1, 1)), yaw = atan2(R[3], R[0]).
+ * They are an output only and never feed back.
+ * Arithmetic: IEEE add, subtract, multiply and divide alone (no fused multiply-add, contraction off, three-term sums left to right) up to the three inverse
+ * trigonometric calls, so pos, R, v, omega and the feet are a pure function of the robot's own inputs -- the same bits at every batch size, position in the batch and
+ * entry -- and an elementwise restatement reproduces them bit for bit.  f64 division in this build is correctly rounded (the compiler's IEEE expansion: the library is
+ * built without any fast-math or unsafe-math flag) and f64 subnormals are kept.
+ * What it is not: first order in h (rotational energy drifts, about 2 % over 5 s at |omega| = 5 rad/s with substeps = 1); no ground, no contact or friction model --
+ * the forces are taken as given, a stance foot does not slip and nothing stops a body below its feet; massless legs.
+ * out: state_out n x state_stride, R_world_out n x 9, foot_abs_out n x 12, all required.  Each may be its input exactly (in place); any other overlap is the
+ * caller's error.  Non-finite inputs of one robot give non-finite outputs of that robot alone.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch: a null handle or config, substeps outside 1 .. 64, dt <= 0 or not
+ * finite, a gravity_z that is not finite, a state_stride other than 12 / 13 / 22, n < 0 or n > max_batch, a null required pointer.  n == 0 is A1MPC_OK and launches
+ * nothing.  The handle gets no state.  Host pointers (staged like the other caller-side entries); the _device entry takes device pointers and is asynchronous on
+ * hip_stream (NULL = the handle's), ordered like every other _device entry: on the stream of the preceding a1mpc_solve_batch_*_device it reads that solve's
+ * d_grf_body_out.
+ */
+typedef struct a1mpc_plant_config { double dt; int32_t substeps; double gravity_z; } a1mpc_plant_config;
+void a1mpc_default_plant_config(a1mpc_plant_config* cfg);   /* 0.0025 (the control tick), 1, -9.8 */
+a1mpc_status a1mpc_plant_step_batch(a1mpc_handle h, const a1mpc_plant_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                    const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, double* state_out,
+                                    double* R_world_out, double* foot_abs_out);
+a1mpc_status a1mpc_plant_step_batch_device(a1mpc_handle h, const a1mpc_plant_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                           const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                           const double* d_ext_wrench, double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
