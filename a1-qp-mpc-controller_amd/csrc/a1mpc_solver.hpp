@@ -419,6 +419,12 @@ struct RowSolver {
     double dt, mu;
     // per-lane constants of the problem
     double Bt[6];  // my column of B~ (force layout); zero on pad lanes
+    // factorize() runs step 0 as a shorter copy of the step behind its loop (no gain work) -- except in the instantiations that sit at the edge of the register file and
+    // answer a second copy of the step with spills: every H = 14 kernel (the update-path instantiations of its fused and latency kernels: 19 and 1 VGPRs to scratch,
+    // refused by the build's resource gate), and those of the H = 16 / 20 kernels that live with bounded scratch already and would get more of it (the update path and
+    // the contact-schedule kernels at H = 16, the twin-pair fall-back at H = 20).  There step 0 stays a full step of the loop whose K_0 store and P_0 update are skipped
+    template <bool UPD>
+    static constexpr bool kPeelStep0 = H != 14 && !(H == 16 && (UPD || !UNI)) && !(H == 20 && !QUAD);
     static constexpr bool kBrowInRegs = ((H <= 10) || TWIN) && !GEN;  // beyond that the per-lane ADMM state alone (6H doubles; 3H for a twin pair) overflows the register file
     static constexpr int NS = TWIN ? (QUAD ? 4 : 2) : 1;  // rows that split the per-lane state of one QP
     static constexpr int HS = H / NS;  // slots of the per-lane state: slot k = step NS k + own
@@ -1427,6 +1433,7 @@ struct RowSolver {
 
     // ================================================================================ Riccati factorisation of
     //   M = c P + sigma D^-2 + A' (E^2 rho) A      (K_s = D M D is OSQP's reduced KKT matrix)
+    template <bool PEEL>
     A1_DEV void factorize() {
         ++nfact;
         const double sigma_f = row_opaque(P.sigma);
@@ -1460,8 +1467,11 @@ struct RowSolver {
         double Btr[6];  // my column of B~, as a DPP source
 #pragma unroll
         for (int k = 0; k < 6; ++k) Btr[k] = row_dpp_ready(Bt[k]);
-#pragma unroll 1
-        for (int t = H - 1; t >= 0; --t) {
+        // One step of the backward recursion.  GAIN = false is step 0, which needs S_0^-1 alone: K_0 is never stored or used (x_0 = 0) and there is no P_0, so
+        // G, F' and K' -- 216 of a step's 708 broadcast multiply-adds -- exist only in the steps t > 0.  Step 0 is a second, shorter copy of the step behind the
+        // loop and not a branch inside it: the loop's code and registers stay those of a loop that has no special step (H = 1, the balance QP: step 0 is the only one)
+        auto step = [&](const int t, auto GAIN) {
+            constexpr bool gain = A1_CV(GAIN);
             double* slot = lds + L::FAC + t * L::SLOT;
             const double wv[3] = {slot[L::K_SZ + 3 * ln], slot[L::K_SZ + 3 * ln + 1], slot[L::K_SZ + 3 * ln + 2]};
             [[maybe_unused]] double Btt[6];
@@ -1472,26 +1482,35 @@ struct RowSolver {
             }
             sync();  // everybody holds W_t before the slot is overwritten
             // G = A' P_{t+1}  (rows mixed across lanes), then GA = G A (columns, lane-local)
-            double G[12];
-            row_dpp_ready12(Pn);
-            static_for<12>([&](auto J) { G[J] = opAT(Pn[J]); });
+            [[maybe_unused]] double G[12];
             // F' = G(:,6:12) B~  (state row-owner)  and  Y = P_{t+1}(6:12,6:12) B~  (valid on the wrench lanes).  B~[k][b] is register k
             // of force lane b (Bt), so every term is a DPP broadcast: no LDS traffic, no staging registers for B~'s rows
-            double Ft[12], Y[12];
+            [[maybe_unused]] double Ft[12];
+            double Y[12];
 #pragma unroll
-            for (int b = 0; b < 12; ++b) { Ft[b] = 0.0; Y[b] = 0.0; }
-            static_for<6>([&](auto K) {
-                static_for<12>([&](auto B) {
-                    fma_bcast<lane_of(A1_CV(B))>(Ft[B], G[6 + K], Btr[K]);
-                    fma_bcast<lane_of(A1_CV(B))>(Y[B], Pn[6 + K], Btr[K]);
+            for (int b = 0; b < 12; ++b) Y[b] = 0.0;
+            if constexpr (gain) {
+#pragma unroll
+                for (int b = 0; b < 12; ++b) Ft[b] = 0.0;
+                row_dpp_ready12(Pn);
+                static_for<12>([&](auto J) { G[J] = opAT(Pn[J]); });
+                static_for<6>([&](auto K) {
+                    static_for<12>([&](auto B) {
+                        fma_bcast<lane_of(A1_CV(B))>(Ft[B], G[6 + K], Btr[K]);
+                        fma_bcast<lane_of(A1_CV(B))>(Y[B], Pn[6 + K], Btr[K]);
+                    });
                 });
-            });
-            G[6] += dt * (cy * G[0] - sy * G[1]);
-            G[7] += dt * (sy * G[0] + cy * G[1]);
-            G[8] += dt * G[2];
-            G[9] += dt * G[3];
-            G[10] += dt * G[4];
-            G[11] += dt * G[5];
+                G[6] += dt * (cy * G[0] - sy * G[1]);
+                G[7] += dt * (sy * G[0] + cy * G[1]);
+                G[8] += dt * G[2];
+                G[9] += dt * G[3];
+                G[10] += dt * G[4];
+                G[11] += dt * G[5];
+            } else {
+                static_for<6>([&](auto K) {
+                    static_for<12>([&](auto B) { fma_bcast<lane_of(A1_CV(B))>(Y[B], Pn[6 + K], Btr[K]); });
+                });
+            }
             // S = W_t + B~' Y   (force row-owner): twelve interleaved chains, each seeded with its W entry
             double S[12];
 #pragma unroll
@@ -1529,30 +1548,35 @@ struct RowSolver {
             }
             // K' = F' S^-1  (state row-owner): K'[i][a] = sum_b F'[i][b] S^-1[b][a]; S^-1[b][a] = register a of force lane b, so every
             // term is one v_fmac_f64_dpp (no LDS round trip)
-            double Kt[12];
+            if constexpr (gain) {  // K_0 is never used (x_0 = 0); its area keeps what it holds (the pad column carries G)
+                double Kt[12];
 #pragma unroll
-            for (int a = 0; a < 12; ++a) Kt[a] = 0.0;
-            row_dpp_ready12(S);
-            static_for<12>([&](auto B) {  // twelve independent accumulator chains
-                static_for<12>([&](auto A_) { fma_bcast<lane_of(A1_CV(B))>(Kt[A_], Ft[B], S[A_]); });
-            });
-            if (wr && t > 0) {  // K_0 is never used (x_0 = 0)
+                for (int a = 0; a < 12; ++a) Kt[a] = 0.0;
+                row_dpp_ready12(S);
+                static_for<12>([&](auto B) {  // twelve independent accumulator chains
+                    static_for<12>([&](auto A_) { fma_bcast<lane_of(A1_CV(B))>(Kt[A_], Ft[B], S[A_]); });
+                });
+                if (wr && (PEEL || t > 0)) {
 #pragma unroll
-                for (int a = 0; a < 12; ++a) slot[a * L::KSTR + ci] = Kt[a];
-            }
-            // P_t = c Q + A' P_{t+1} A - F' K:  K[a][j] = register a of state lane j
-            if (t > 0) {
-                static_for<12>([&](auto J) {
-                    Pn[J] = G[J];
-                    fma_bcast_leg<0, A1_CV(J) / 3>(Pn[J], qdc[A1_CV(J) % 3], one0);
-                });
-                row_dpp_ready12(Kt);
-                static_for<12>([&](auto A_) {
-                    static_for<12>([&](auto J) { fnma_bcast<lane_of(A1_CV(J))>(Pn[J], Ft[A_], Kt[A_]); });
-                });
+                    for (int a = 0; a < 12; ++a) slot[a * L::KSTR + ci] = Kt[a];
+                }
+                // P_t = c Q + A' P_{t+1} A - F' K:  K[a][j] = register a of state lane j
+                if (PEEL || t > 0) {
+                    static_for<12>([&](auto J) {
+                        Pn[J] = G[J];
+                        fma_bcast_leg<0, A1_CV(J) / 3>(Pn[J], qdc[A1_CV(J) % 3], one0);
+                    });
+                    row_dpp_ready12(Kt);
+                    static_for<12>([&](auto A_) {
+                        static_for<12>([&](auto J) { fnma_bcast<lane_of(A1_CV(J))>(Pn[J], Ft[A_], Kt[A_]); });
+                    });
+                }
             }
             sync();  // K_t and S_t^-1 of this step are in LDS before the next step reuses the registers' sources
-        }
+        };
+#pragma unroll 1
+        for (int t = H - 1; t >= (PEEL ? 1 : 0); --t) step(t, std::true_type{});
+        if constexpr (PEEL) step(0, std::false_type{});
 #pragma unroll
         for (int b = 0; b < 12; ++b) Brw[b] = kBrowInRegs ? brow[b] : 0.0;
         need_factor = false;
@@ -2070,7 +2094,7 @@ struct RowSolver {
 #endif
         [[maybe_unused]] long long pf0_ = 0;
         if constexpr (CLK) pf0_ = row_clock();
-        if (need_factor) factorize();
+        if (need_factor) factorize<kPeelStep0<UPD>>();
         if constexpr (CLK) pfX += row_clock() - pf0_;
 #ifdef A1X_CLK
         clkX += clock64() - tf_;
