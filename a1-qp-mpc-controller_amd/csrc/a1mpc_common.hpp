@@ -37,7 +37,8 @@ constexpr size_t lds_bytes(int rows) { return sizeof(double) * rows * Layout<H>:
 // issue slots with 2 or 4 live rows, so 2 rows x 4 waves per CU loses nothing and each row waits for only one neighbour's
 // factorisation passes (measured: +5 % at 4096 QPs, +4 % at 32768).  From H = 16 on LDS allows four QPs per CU at most: one QP (a main / twin pair of rows) per
 // wavefront then puts them on four SIMDs instead of two -- no more QPs in flight, but no row waits for a wave-mate's hand-over or factor pass any more and the LDS
-// conflicts between the two images go (8192 x h16 first solve 4.62 -> 4.41 ms, 16 384 x h20 10.35 -> 10.04 ms).  A1MPC_ROWS_PER_WG = 1 | 2 | 4 overrides.
+// conflicts between the two images go (8192 x h16 first solve 4.62 -> 4.41 ms, 16 384 x h20 10.35 -> 10.04 ms).  The other layouts (1 | 2 | 4 QPs per wavefront at every
+// horizon) were measured and lost; only these defaults are built.
 constexpr int default_rows_per_wg(int horizon) { return horizon >= 16 ? 1 : 2; }
 // Horizons compiled in (the reference fixes PLAN_HORIZON = 10 at compile time, S/A1Params.h:26; a run-time value here).  1 / 10 / 16 / 20 are the tuned ones (the
 // balance-QP analogue, the reference's horizon, BASELINE configs[3] / [4]): fast path AND general path, every kernel variant.  The other even horizons up to 14 run the
@@ -52,19 +53,6 @@ constexpr int default_rows_per_wg(int horizon) { return horizon >= 16 ? 1 : 2; }
 // (H, QPs per wavefront of the general path's kernels): every multi-step horizon
 #define A1MPC_GEN_HORIZONS(X) X(4, 2) X(6, 2) X(8, 2) X(10, 2) X(12, 2) X(14, 2) X(16, 1) X(20, 1)
 #define A1MPC_HORIZON_LIST "1, 4, 6, 8, 10, 12, 14, 16 or 20"
-// The shipped build instantiates the kernels for the default rows per workgroup only (the other two layouts were measured and lost, above; every extra layout of
-// the H = 16 / 20 kernels costs a minute of compile time): the override is honoured by -DA1MPC_ALL_ROWS tuning builds.
-static int rows_per_wg(int horizon) {
-#ifndef A1MPC_ALL_ROWS
-    return default_rows_per_wg(horizon);
-#endif
-    static int r = [] {
-        const char* e = getenv("A1MPC_ROWS_PER_WG");
-        const int v = e ? atoi(e) : 0;
-        return (v == 1 || v == 2 || v == 4) ? v : 0;
-    }();
-    return r ? r : default_rows_per_wg(horizon);
-}
 
 extern thread_local std::string g_last_error;   // (a1mpc_hip.hip)
 inline a1mpc_status fail(a1mpc_status s, const std::string& msg) { g_last_error = msg; return s; }
@@ -114,10 +102,13 @@ struct RoctxRange {
     RoctxRange& operator=(const RoctxRange&) = delete;
 };
 
-// per-device caches (occupancy, attribute-set flags) are shared by every handle of the process: handles of different threads are independent (a1mpc.h), so they are guarded
-extern std::mutex g_cache_mu;   // (a1mpc_hip.hip)
-// dynamic-LDS limit of a kernel, once per device and kernel
-a1mpc_status set_lds_attr(const void* fn, size_t bytes);
+extern std::mutex g_cache_mu;   // (a1mpc_hip.hip) a1mpc_create's one-time warm-up of the runtime, per device
+
+// ---- the launch layer: one table per process of (kernel, device) -> dynamic-LDS limit set, resident workgroups; one mutex of its own (a1mpc_hip.hip).  Handles of
+// different threads are independent (a1mpc.h) and may launch at the same time.  `dev` is the current device: a launch function asks for it ONCE (hipGetDevice) and hands it on.
+a1mpc_status set_lds_attr(int dev, const void* fn, size_t bytes);                                    // the dynamic-LDS limit of a kernel, once per device and kernel
+a1mpc_status resident_workgroups(int dev, const void* fn, int threads, size_t lds, int* out);        // ... and how many of its workgroups the device holds at once (occupancy query, cached)
+
 
 // the CU-wide ADMM kernel (a1mpc_admm_cu_kernel; H = 16): one workgroup of 256 threads and five images per CU.  A1MPC_CU_WIDE=0 falls back to the one-wave kernels (A/B runs)
 inline bool cu_wide_enabled() {
@@ -140,6 +131,18 @@ inline bool cu_quad_enabled() {
     return on && quad_enabled();
 }
 
+struct Geometry { int threads; int qps; size_t lds; };   // of one workgroup: threads, QPs it works on, dynamic LDS bytes
+// ... of the split pipeline's persistent ADMM kernel: CU-wide (where the horizon has that kernel) or one wavefront of default_rows_per_wg QPs (twin rows: a full wavefront).
+// The one source of these numbers: select_admm (a1mpc_kernels.hpp) launches with them, a1mpc_kernel_info reports them
+template <int H>
+constexpr Geometry admm_geometry(bool cu_wide) {
+    constexpr int R = default_rows_per_wg(H), Q = cu_wide_qps(H);
+    if (Q > 0 && cu_wide) return {256, Q, lds_bytes<H>(Q)};
+    return {twin_rows(H, kModeMpc, R) ? 64 : 16 * R, R, lds_bytes<H>(R)};
+}
+template <int H>
+Geometry admm_geometry() { return admm_geometry<H>(cu_wide_enabled()); }   // ... as this process runs it
+
 // Did the launch just issued run a profiling (CLK) instantiation?  Set by the launch functions, read by solve_device_impl right after them (same thread): only then does
 // the handle's stage record describe the solve (a fallback kernel without stamps must not leave a stale or uninitialised record behind as "profiled").
 extern thread_local bool g_clk_ran;   // (a1mpc_hip.hip)
@@ -147,7 +150,7 @@ extern thread_local bool g_clk_ran;   // (a1mpc_hip.hip)
 // A lone handle wants the seventh QP (4096 x h10 first solves 2.87 against 2.76 M/s).  A slot of a TWO-slot pipeline wants the 24 KB: the other slot's set-up workgroups
 // (11.8 KB each) then run BESIDE its persistent rows instead of waiting for them to retire -- 3.57-3.62 against 3.37-3.41 M/s with two batches in flight, reproducibly
 // (profiles/r06_general_pipeline.md); with three slots the CU-wide kernel is ahead again by 1.4 %.  Set by solve_device_impl from the handle's pipeline depth for the duration
-// of a launch, read by launch_gen_split_rows (same thread).  Scheduling only: the two kernels agree bit for bit (tested).  A1MPC_GEN_PIPE_ONE_WAVE=0 ignores the hint (A/B runs)
+// of a launch, read by select_admm_gen (same thread).  Scheduling only: the two kernels agree bit for bit (tested).  A1MPC_GEN_PIPE_ONE_WAVE=0 ignores the hint (A/B runs)
 extern thread_local bool g_gen_prefer_one_wave;   // (a1mpc_hip.hip)
 // horizons whose fused / latency kernels have a profiling instantiation (the closed-loop tick and the batch-1 tick of the headline horizon; every further horizon costs a minute of compile time)
 constexpr bool tick_clk_horizon(int h) { return h == 10; }
@@ -168,7 +171,7 @@ template <int H> a1mpc_status resident_rows(int* out);                          
 template <int H, int MODE> a1mpc_status launch(const KernelArgs& a, hipStream_t stream);                                             // a1mpc_k_h<H>_fused.hip
 template <int H, int ROWS> a1mpc_status launch_gen_rows(const KernelArgs& a, hipStream_t stream);                                    // a1mpc_k_gen<H>_fused.hip
 template <int H, int ROWS> a1mpc_status resident_workgroups_gen(int* out);                                                          // a1mpc_k_gen<H>_split.hip
-template <int H, int ROWS> a1mpc_status launch_gen_split_rows(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid, int res);   // a1mpc_k_gen<H>_split.hip
+template <int H, int ROWS> a1mpc_status launch_gen_split_rows(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid);   // a1mpc_k_gen<H>_split.hip
 a1mpc_status launch_fused_queue(const KernelArgs& a, int* counter, hipStream_t stream);                                               // a1mpc_k_h10_split.hip (the round-5 trial kernel)
 // the two small non-template kernels every pipeline shares live in a1mpc_hip.hip behind these:
 void launch_order_kernel(int n, const int32_t* cost, int32_t* order, hipStream_t stream);   // a1mpc_order_kernel: the queue order of a solve, longest first

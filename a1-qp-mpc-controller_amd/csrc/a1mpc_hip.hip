@@ -2,8 +2,8 @@
 // the dense-QP formation entry, the queue-order kernel).
 //
 // The solver's kernels live in csrc/a1mpc_kernels.hpp and are compiled as one translation unit per (horizon, pipeline): csrc/a1mpc_k_*.hip (round 6; build.py compiles the
-// units in parallel).  This unit sees only the DECLARATIONS of their launch entry points (csrc/a1mpc_common.hpp) and decides which way a batch goes (launch_mpc,
-// solve_device_impl): the latency kernel (<= 256 QPs: the rows of a wave share one QP's set-up), the fused kernel (up to the resident rows: one row pair = one QP from
+// units in parallel).  This unit sees only the DECLARATIONS of their launch entry points (csrc/a1mpc_common.hpp), reaches them through ONE per-horizon table (ops_of), holds the
+// launch layer's (kernel, device) table (set_lds_attr, resident_workgroups) and decides which way a batch goes (launch_mpc, solve_device_impl): the latency kernel (<= 256 QPs: the rows of a wave share one QP's set-up), the fused kernel (up to the resident rows: one row pair = one QP from
 // inputs to outputs; also warm-started ticks of a known batch) or the split pipeline (set-up kernel -> queue-order kernel -> persistent ADMM rows that drain the queue
 // longest-first); the general path (per-step feet / contact schedules) has the same three.  The QPs of a batch are independent; nothing is shared between workgroups except the
 // read-only (alpha/beta) table and the queue counter, so the blockIdx -> XCD mapping is irrelevant here (no L2 reuse to localise).
@@ -11,9 +11,11 @@
 // There is no CPU path in this file: without a HIP device every entry point fails.
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is dlopen()ed by a1mpc_sharded_create(transport = 1), never linked
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
+#include <map>
 #include <new>
 
 #include "a1mpc_common.hpp"
@@ -789,74 +791,93 @@ thread_local std::string g_last_error;
 std::mutex g_cache_mu;
 thread_local bool g_clk_ran = false;
 thread_local bool g_gen_prefer_one_wave = false;
-// dynamic-LDS limit of a kernel, once per device and kernel
-a1mpc_status set_lds_attr(const void* fn, size_t bytes) {
-    static std::vector<std::pair<const void*, int>> done;
-    static std::mutex mu;   // handles of different threads may launch at the same time
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    A1_HIP(hipGetDevice(&dev));
-    for (const auto& d : done) if (d.first == fn && d.second == dev) return A1MPC_OK;
-    A1_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
-    done.emplace_back(fn, dev);
+// ---- the launch layer's table (a1mpc_common.hpp): (kernel, device) -> resident workgroups.  An entry exists once the kernel's dynamic-LDS limit is set on that device
+// and holds 0 until its occupancy has been asked for.  One mutex: handles of different threads may launch at the same time
+static std::mutex g_kernel_mu;
+static std::map<std::pair<const void*, int>, int> g_kernels;
+static a1mpc_status kernel_entry(int dev, const void* fn, size_t lds, int** resident) {   // (g_kernel_mu held)
+    auto it = g_kernels.find({fn, dev});
+    if (it == g_kernels.end()) {
+        A1_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        it = g_kernels.emplace(std::make_pair(fn, dev), 0).first;
+    }
+    *resident = &it->second;
+    return A1MPC_OK;
+}
+a1mpc_status set_lds_attr(int dev, const void* fn, size_t bytes) {
+    std::lock_guard<std::mutex> lock(g_kernel_mu);
+    int* resident = nullptr;
+    return kernel_entry(dev, fn, bytes, &resident);
+}
+a1mpc_status resident_workgroups(int dev, const void* fn, int threads, size_t lds, int* out) {
+    std::lock_guard<std::mutex> lock(g_kernel_mu);
+    int* resident = nullptr;
+    if (a1mpc_status st = kernel_entry(dev, fn, lds, &resident); st != A1MPC_OK) return st;
+    if (!*resident) {
+        int per_cu = 0, cus = 0;
+        A1_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds));
+        A1_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        *resident = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+    }
+    *out = *resident;
     return A1MPC_OK;
 }
 
-static size_t carry_stride(int horizon) {
-    switch (horizon) {
-#define A1_CASE(H) case H: return Carry<H>::STRIDE;
-        A1MPC_MULTI_STEP_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return 0;  // (horizon 1: the update path does not apply -- warm_start = 2 behaves like 1)
+// ---- what a horizon compiled in has: its record sizes and the entry points of its a1mpc_k_*.hip units
+struct HorizonOps {
+    int horizon;
+    size_t carry_stride;   // doubles per QP of the update path's carry (0 at horizon 1: the update path does not apply -- warm_start = 2 behaves like 1)
+    size_t prep_stride, prep_stride_gen;   // ... of the hand-off records of the two split pipelines
+    Geometry (*admm_geometry)();   // of the persistent ADMM kernel large batches run (a1mpc_kernel_info)
+    a1mpc_status (*launch_split)(const KernelArgs&, double*, int*, hipStream_t, hipEvent_t);
+    a1mpc_status (*resident_rows)(int*);
+    a1mpc_status (*launch)(const KernelArgs&, hipStream_t);
+    // the general path (every multi-step horizon; gen_qps = QPs per wavefront of its kernels, 0 = none).  LDS per QP (round 6: the per-step bounds left the image): 22.7 KB
+    // (H = 10: six QPs per CU in one-wave workgroups, seven in the CU-wide persistent kernel), 35.9 KB (H = 16: four, one per wavefront like the fast path's), 44.7 KB (H = 20:
+    // three, one row per workgroup) -- which also leaves 13 / 26 KB of a CU's LDS free at H = 16 / 20: the set-up kernel of a second batch in flight (11.7 / 15.7 KB per
+    // workgroup) now runs BESIDE the persistent kernel instead of behind it (profiles/r06_general_pipeline.md)
+    int gen_qps;
+    a1mpc_status (*resident_workgroups_gen)(int*);
+    a1mpc_status (*launch_gen_split)(const KernelArgs&, double*, int*, hipStream_t, hipEvent_t);
+    a1mpc_status (*launch_gen)(const KernelArgs&, hipStream_t);
+};
+template <int H>
+static HorizonOps fast_ops() {
+    size_t carry = 0;
+    if constexpr (H > 1) carry = Carry<H>::STRIDE;
+    return {H, carry, Prep<H>::STRIDE, 0, &admm_geometry<H>, &launch_split<H>, &resident_rows<H>, &launch<H, kModeMpc>, 0, nullptr, nullptr, nullptr};
 }
-static size_t prep_stride(int horizon) {
-    switch (horizon) {
-#define A1_CASE(H) case H: return Prep<H>::STRIDE;
-        A1MPC_FAST_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return 0;
+template <int H, int R>
+static void add_gen_ops(HorizonOps* o) {
+    o->prep_stride_gen = Prep<H>::STRIDE_GEN; o->gen_qps = R;
+    o->resident_workgroups_gen = &resident_workgroups_gen<H, R>; o->launch_gen_split = &launch_gen_split_rows<H, R>; o->launch_gen = &launch_gen_rows<H, R>;
 }
-static size_t prep_stride_gen(int horizon) {
-    switch (horizon) {
-#define A1_CASE(H, R) case H: return Prep<H>::STRIDE_GEN;
-        A1MPC_GEN_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return 0;
+static std::vector<HorizonOps> horizon_table() {
+    std::vector<HorizonOps> t;
+    const auto at = [&t](int h) { for (HorizonOps& o : t) if (o.horizon == h) return &o; return static_cast<HorizonOps*>(nullptr); };
+#define A1_FAST_OPS(H) t.push_back(fast_ops<H>());
+    A1MPC_FAST_HORIZONS(A1_FAST_OPS)
+#undef A1_FAST_OPS
+#define A1_GEN_OPS(H, R) add_gen_ops<H, R>(at(H));
+    A1MPC_GEN_HORIZONS(A1_GEN_OPS)
+#undef A1_GEN_OPS
+    return t;
 }
+static const HorizonOps* ops_of(int horizon) {   // null: a horizon that is not compiled in
+    static const std::vector<HorizonOps> table = horizon_table();
+    for (const HorizonOps& o : table) if (o.horizon == horizon) return &o;
+    return nullptr;
+}
+static size_t carry_stride(int horizon) { const HorizonOps* o = ops_of(horizon); return o ? o->carry_stride : 0; }
+static a1mpc_status no_general_path() { return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "per-step feet (foot_stride = 12) and a separate A_c yaw need a horizon > 1"); }
 // rows of the general path's ADMM kernel that are resident at once (0: horizon without a general path)
-static a1mpc_status resident_rows_gen(int horizon, int* rows) {
+static a1mpc_status resident_rows_gen(const HorizonOps& o, int* rows) {
     int wg = 0;
-    a1mpc_status st = A1MPC_OK;
     *rows = 0;
-    switch (horizon) {
-#define A1_CASE(H, R) case H: st = resident_workgroups_gen<H, R>(&wg); *rows = R * wg; break;
-        A1MPC_GEN_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
+    if (!o.gen_qps) return A1MPC_OK;
+    const a1mpc_status st = o.resident_workgroups_gen(&wg);
+    *rows = o.gen_qps * wg;
     return st;
-}
-static a1mpc_status launch_gen_split(int horizon, const KernelArgs& a, double* prep, int* counter, hipStream_t s, hipEvent_t mid) {
-    int wg = 0;
-    switch (horizon) {
-#define A1_CASE(H, R) case H: if (a1mpc_status st = resident_workgroups_gen<H, R>(&wg); st != A1MPC_OK) return st; return launch_gen_split_rows<H, R>(a, prep, counter, s, mid, wg);
-        A1MPC_GEN_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "per-step feet (foot_stride = 12) and a separate A_c yaw need a horizon > 1");
-}
-// LDS per QP (round 6: the per-step bounds left the image): 22.7 KB (H = 10: six QPs per CU in one-wave workgroups, seven in the CU-wide persistent kernel), 35.9 KB (H = 16: four,
-// one per wavefront like the fast path's), 44.7 KB (H = 20: three, one row per workgroup) -- which also leaves 13 / 26 KB of a CU's LDS free at H = 16 / 20: the set-up kernel of a
-// second batch in flight (11.7 / 15.7 KB per workgroup) now runs BESIDE the persistent kernel instead of behind it (profiles/r06_general_pipeline.md)
-static a1mpc_status launch_gen(int horizon, const KernelArgs& a, hipStream_t s) {
-    switch (horizon) {
-#define A1_CASE(H, R) case H: return launch_gen_rows<H, R>(a, s);
-        A1MPC_GEN_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "per-step feet (foot_stride = 12) and a separate A_c yaw need a horizon > 1");
 }
 
 static bool warm_fused_enabled() {
@@ -873,18 +894,12 @@ static int warm_fused_max(int horizon) {
 static constexpr int kScheduleMinBatch = 1024;  // below this every QP is resident at once and the order cannot matter
 
 // does a batch of n QPs go through the split pipeline?
-static a1mpc_status use_split_pipeline(int horizon, int n, bool have_prep, bool* split) {
+static a1mpc_status use_split_pipeline(const HorizonOps& o, int n, bool have_prep, bool* split) {
     *split = false;
     if (!have_prep || pipeline_mode() == 2) return A1MPC_OK;
     if (pipeline_mode() == 1) { *split = true; return A1MPC_OK; }
     int rows = 0;
-    a1mpc_status st = A1MPC_OK;
-    switch (horizon) {
-#define A1_CASE(H) case H: st = resident_rows<H>(&rows); break;
-        A1MPC_FAST_HORIZONS(A1_CASE)
-#undef A1_CASE
-        default: return A1MPC_OK;
-    }
+    const a1mpc_status st = o.resident_rows(&rows);
     *split = n > rows;
     return st;
 }
@@ -893,34 +908,14 @@ static bool fused_queue_enabled() {
     static const bool on = [] { const char* e = getenv("A1MPC_FUSED_QUEUE"); return e && !strcmp(e, "1"); }();
     return on;
 }
-static a1mpc_status launch_mpc(int horizon, const KernelArgs& a, double* prep, int* counter, hipStream_t s, bool split, hipEvent_t mid) {
+static a1mpc_status launch_mpc(const HorizonOps& o, const KernelArgs& a, double* prep, int* counter, hipStream_t s, bool split, hipEvent_t mid) {
     RoctxRange range(split ? "a1mpc solve (split pipeline)" : "a1mpc solve (fused)");
-    if (split && counter && horizon == 10 && fused_queue_enabled() && a.carry == nullptr && a.clk == nullptr) {
+    if (split && counter && o.horizon == 10 && fused_queue_enabled() && a.carry == nullptr && a.clk == nullptr) {
         if (mid) A1_HIP(hipEventRecord(mid, s));
         return launch_fused_queue(a, counter, s);
     }
-    if (split && prep && counter) {
-        switch (horizon) {
-#define A1_CASE(H) case H: return launch_split<H>(a, prep, counter, s, mid);
-            A1MPC_FAST_HORIZONS(A1_CASE)
-#undef A1_CASE
-        }
-    }
-    switch (horizon) {
-#define A1_CASE(H) case H: return launch<H, kModeMpc>(a, s);
-        A1MPC_FAST_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "horizon must be " A1MPC_HORIZON_LIST);
-}
-static size_t lds_bytes_of(int horizon) {
-    const int r = rows_per_wg(horizon);
-    switch (horizon) {
-#define A1_CASE(H) case H: return lds_bytes<H>(r);
-        A1MPC_FAST_HORIZONS(A1_CASE)
-#undef A1_CASE
-    }
-    return 0;
+    if (split && prep && counter) return o.launch_split(a, prep, counter, s, mid);
+    return o.launch(a, s);
 }
 
 static void to_device_params(const a1mpc_config& c, DeviceParams* p) {
@@ -2682,7 +2677,7 @@ static bool small_batch(a1mpc_handle h, int32_t n) { return n <= zero_copy_max()
 a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t device, a1mpc_handle* out) {
     if (!cfg || !out || max_batch <= 0 || device < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null config/out or bad batch/device");
     *out = nullptr;
-    if (lds_bytes_of(cfg->horizon) == 0) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "horizon must be " A1MPC_HORIZON_LIST);
+    if (ops_of(cfg->horizon) == nullptr) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "horizon must be " A1MPC_HORIZON_LIST);
     if (const char* why = invalid_config(*cfg)) return fail(A1MPC_ERR_INVALID_ARGUMENT, why);   // (before any device query: a bad configuration is reported as such on every machine)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(A1MPC_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
@@ -2737,7 +2732,7 @@ a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t de
     A1_TRY(hipMemset(h->d_wx, 0, n * 12 * H * sizeof(double)));
     A1_TRY(hipMemset(h->d_wy, 0, n * 20 * H * sizeof(double)));
     A1_TRY(hipMemset(h->d_rho, 0, n * sizeof(double)));
-    if (pipeline_mode() != 2) A1_TRY(hipMalloc(&h->d_prep, n * prep_stride(H) * sizeof(double)));
+    if (pipeline_mode() != 2) A1_TRY(hipMalloc(&h->d_prep, n * ops_of(H)->prep_stride * sizeof(double)));
     A1_TRY(hipMalloc(&h->d_counter, sizeof(int)));
     A1_TRY(hipMalloc(&h->d_order, n * sizeof(int32_t)));
     A1_TRY(hipMalloc(&h->d_cost, n * sizeof(int32_t)));
@@ -2757,10 +2752,9 @@ a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t de
     { void* dp = nullptr; if (hipHostGetDevicePointer(&dp, h->h_pin, 0) == hipSuccess) h->d_pin = static_cast<char*>(dp); else (void)hipGetLastError(); }
     // One-time, per process: the first launches / copies through a fresh HIP runtime cost milliseconds (code-object load, pool set-up);
     // a 400 Hz loop should not pay that on its first tick (measured 5 ms -> 0.4 ms), so the tick's operation mix is exercised here.
-    static bool runtime_warmed_dev[64] = {};   // per device: a sharded handle (a1mpc_sharded_*) creates one engine handle on every GPU of the node
+    static std::vector<int> runtime_warmed;   // the devices done: a sharded handle (a1mpc_sharded_*) creates one engine handle on every GPU of the node
     std::unique_lock<std::mutex> warm_lock(g_cache_mu);   // (handles may be created from several threads)
-    bool& runtime_warmed = runtime_warmed_dev[device < 64 ? device : 63];
-    if (!runtime_warmed) {
+    if (std::find(runtime_warmed.begin(), runtime_warmed.end(), device) == runtime_warmed.end()) {
         for (int i = 0; i < 256; ++i) {  // the operation mix of a tick: copies both ways from pinned memory, memset, launches, events
             A1_TRY(hipMemcpyAsync(h->d_x0, h->h_pin, 8, hipMemcpyHostToDevice, h->stream));
             A1_TRY(hipMemsetAsync(h->d_counter, 0, sizeof(int), h->stream));
@@ -2772,7 +2766,7 @@ a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t de
             if ((i & 63) == 63) A1_TRY(hipStreamSynchronize(h->stream));
         }
         A1_TRY(hipStreamSynchronize(h->stream));
-        runtime_warmed = true;
+        runtime_warmed.push_back(device);
     }
     warm_lock.unlock();
 #undef A1_TRY
@@ -3010,6 +3004,7 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->stream;
     A1_ORDER(h, s);
     h->clk_n = 0; h->clk_tick = false;   // (set again below when this solve runs a profiling instantiation)
+    const HorizonOps& ops = *ops_of(h->cfg.horizon);   // (a handle's horizon is compiled in: a1mpc_create)
     KernelArgs a;
     std::memset(&a, 0, sizeof a);
     a.P = h->dp; a.tab = h->d_tab; a.n = n;
@@ -3033,7 +3028,7 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
         // a batch beyond the resident rows of the general path's ADMM kernel runs its split pipeline (set-up kernel + persistent rows on a queue, like the
         // fast path); its hand-off records (B~w_t of every step included) live in a buffer of their own, allocated on first use
         int rows_gen = 0;
-        if (a1mpc_status st0 = resident_rows_gen(h->cfg.horizon, &rows_gen); st0 != A1MPC_OK) return st0;
+        if (a1mpc_status st0 = resident_rows_gen(ops, &rows_gen); st0 != A1MPC_OK) return st0;
         bool split_gen = pipeline_mode() != 2 && rows_gen > 0 && (pipeline_mode() == 1 || n > rows_gen) && h->d_counter != nullptr;
         // warm_start = 2: the FUSED general kernels follow the update path like the fast path's (round 5: batches within the resident rows).  Round 6: every batch size --
         // an update-path batch beyond the resident rows runs the fused kernel as well, in as many rounds as it takes (the hardware dispatches the grid's workgroups as
@@ -3048,7 +3043,7 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
             h->last_ws_mode = 1;
         }
         if (split_gen && !h->d_prep_gen) {
-            A1_HIP(hipMalloc(&h->d_prep_gen, static_cast<size_t>(h->max_batch) * prep_stride_gen(h->cfg.horizon) * sizeof(double)));
+            A1_HIP(hipMalloc(&h->d_prep_gen, static_cast<size_t>(h->max_batch) * ops.prep_stride_gen * sizeof(double)));
         }
         const bool hints_gen = h->schedule && split_gen && n >= kScheduleMinBatch && h->d_order != nullptr && h->d_cost != nullptr;
         a.order = hints_gen ? h->d_order : nullptr;
@@ -3059,12 +3054,12 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
         if (split_gen) {
             static const bool pipe_hint = [] { const char* e = getenv("A1MPC_GEN_PIPE_ONE_WAVE"); return !(e && !strcmp(e, "0")); }();
             g_gen_prefer_one_wave = pipe_hint && h->pipeline_depth == 2;
-            const a1mpc_status stg = launch_gen_split(h->cfg.horizon, a, h->d_prep_gen, h->d_counter, s, h->timing ? h->ev_mid : nullptr);
+            const a1mpc_status stg = ops.launch_gen_split(a, h->d_prep_gen, h->d_counter, s, h->timing ? h->ev_mid : nullptr);   // (split_gen: the horizon has a general path)
             g_gen_prefer_one_wave = false;
             if (stg != A1MPC_OK) return stg;
             if (hints_gen) h->hint_n = -n;   // the cost buffer now holds this batch's costs: the next general-path solve of this size is ordered by them
         } else {
-            if (a1mpc_status stg = launch_gen(h->cfg.horizon, a, s); stg != A1MPC_OK) return stg;
+            if (a1mpc_status stg = ops.launch_gen ? ops.launch_gen(a, s) : no_general_path(); stg != A1MPC_OK) return stg;
         }
         if (h->timing) A1_HIP(hipEventRecord(h->ev1, s));
         h->timed = h->timing;
@@ -3075,7 +3070,7 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
     // this handle (the same robots tick after tick); the first solve of a batch size is ordered by the set-up kernel's cost guess
     // (RowSolver::predict_cost).  Scheduling only.
     bool split = false;
-    if (a1mpc_status st0 = use_split_pipeline(h->cfg.horizon, n, h->d_prep != nullptr, &split); st0 != A1MPC_OK) return st0;
+    if (a1mpc_status st0 = use_split_pipeline(ops, n, h->d_prep != nullptr, &split); st0 != A1MPC_OK) return st0;
     // Warm-started ticks of the same robots (the closed-loop regime: second and later ticks of a batch size) take ~25 iterations each, all alike: nothing is left
     // for the queue to balance, and the fused kernel -- set-up and solve in one launch, no hand-off through memory, no kernel boundary for the rows to idle at --
     // wins up to a few rounds of the resident rows (4096 x h10: 0.397 -> 0.350 ms per tick, 8192: 0.665 -> 0.652; profiles/r04_warm_ticks_fused_vs_split.txt).
@@ -3107,7 +3102,7 @@ static a1mpc_status solve_device_impl(a1mpc_handle h, int32_t n, const double* d
         a.clk = h->d_clk;
     }
     g_clk_ran = false;
-    a1mpc_status st = launch_mpc(h->cfg.horizon, a, h->d_prep, h->d_counter, s, split, h->timing ? h->ev_mid : nullptr);
+    a1mpc_status st = launch_mpc(ops, a, h->d_prep, h->d_counter, s, split, h->timing ? h->ev_mid : nullptr);
     if (st != A1MPC_OK) return st;
     if (a.clk != nullptr && g_clk_ran) { h->clk_n = n; h->clk_tick = !split; }   // (a kernel without stamps ran: the record stays "not profiled")
     if (hints) h->hint_n = n;   // the cost buffer now holds this batch's costs: the next solve of this size is ordered by them (sorted in front of its ADMM kernel)
@@ -4099,17 +4094,12 @@ a1mpc_status a1mpc_last_nfact(a1mpc_handle h, int32_t n, int32_t* nfact_out) {
 a1mpc_status a1mpc_kernel_info(a1mpc_handle h, int32_t* lds_bytes_per_workgroup, int32_t* qps_per_workgroup,
                                int32_t* threads_per_workgroup) {
     if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
-    // the geometry of the persistent ADMM kernel large batches run (the fused / latency kernels of small batches: one wavefront of rows_per_wg QPs)
-    if (cu_wide_qps(h->cfg.horizon) > 0 && cu_wide_enabled() && rows_per_wg(h->cfg.horizon) == default_rows_per_wg(h->cfg.horizon)) {   // h = 16: one CU-wide workgroup, five QPs
-        const int q = cu_wide_qps(h->cfg.horizon);
-        if (lds_bytes_per_workgroup) *lds_bytes_per_workgroup = static_cast<int32_t>(lds_bytes_of(h->cfg.horizon) / rows_per_wg(h->cfg.horizon) * q);
-        if (qps_per_workgroup) *qps_per_workgroup = q;
-        if (threads_per_workgroup) *threads_per_workgroup = 256;
-        return A1MPC_OK;
-    }
-    if (lds_bytes_per_workgroup) *lds_bytes_per_workgroup = static_cast<int32_t>(lds_bytes_of(h->cfg.horizon));
-    if (qps_per_workgroup) *qps_per_workgroup = rows_per_wg(h->cfg.horizon);
-    if (threads_per_workgroup) *threads_per_workgroup = h->cfg.horizon > 1 && rows_per_wg(h->cfg.horizon) <= 2 ? 64 : 16 * rows_per_wg(h->cfg.horizon);  // (twin rows: a full wavefront)
+    // the geometry of the persistent ADMM kernel large batches run, from where its launch takes it (the fused / latency kernels of small batches: one wavefront of
+    // default_rows_per_wg QPs)
+    const Geometry g = ops_of(h->cfg.horizon)->admm_geometry();
+    if (lds_bytes_per_workgroup) *lds_bytes_per_workgroup = static_cast<int32_t>(g.lds);
+    if (qps_per_workgroup) *qps_per_workgroup = g.qps;
+    if (threads_per_workgroup) *threads_per_workgroup = g.threads;
     return A1MPC_OK;
 }
 
@@ -4181,7 +4171,7 @@ a1mpc_status a1mpc_sharded_create(const a1mpc_config* cfg, int32_t max_batch, co
                                   a1mpc_sharded* out) {
     if (!cfg || !out || max_batch <= 0 || (transport != 0 && transport != 1)) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null config/out, bad batch or transport");
     *out = nullptr;
-    if (lds_bytes_of(cfg->horizon) == 0) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "horizon must be " A1MPC_HORIZON_LIST);
+    if (ops_of(cfg->horizon) == nullptr) return fail(A1MPC_ERR_UNSUPPORTED_HORIZON, "horizon must be " A1MPC_HORIZON_LIST);
     if (const char* why = invalid_config(*cfg)) return fail(A1MPC_ERR_INVALID_ARGUMENT, why);
     int visible = 0;
     if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) return fail(A1MPC_ERR_NO_DEVICE, "hipGetDeviceCount found no device");

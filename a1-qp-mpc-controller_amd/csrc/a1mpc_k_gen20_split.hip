@@ -5,7 +5,7 @@
 namespace a1mpc {
 
 template a1mpc_status resident_workgroups_gen<20, 1>(int*);
-template a1mpc_status launch_gen_split_rows<20, 1>(const KernelArgs&, double*, int*, hipStream_t, hipEvent_t, int);
+template a1mpc_status launch_gen_split_rows<20, 1>(const KernelArgs&, double*, int*, hipStream_t, hipEvent_t);
 
 
 }  // namespace a1mpc

@@ -6,7 +6,7 @@
 namespace a1mpc {
 
 template a1mpc_status resident_workgroups_gen<6, 2>(int*);
-template a1mpc_status launch_gen_split_rows<6, 2>(const KernelArgs&, double*, int*, hipStream_t, hipEvent_t, int);
+template a1mpc_status launch_gen_split_rows<6, 2>(const KernelArgs&, double*, int*, hipStream_t, hipEvent_t);
 template a1mpc_status launch_gen_rows<6, 2>(const KernelArgs&, hipStream_t);
 
 

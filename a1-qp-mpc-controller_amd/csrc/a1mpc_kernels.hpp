@@ -1,5 +1,6 @@
 // a1mpc_kernels.hpp -- the gfx950 __global__ templates of the solver and the host functions that launch them.  Included by the a1mpc_k_*.hip units ONLY (each explicitly
 // instantiates the entry points of one horizon and pipeline, declared in a1mpc_common.hpp); a1mpc_hip.hip never sees a definition from here.
+// Host side (end of the file): one select_* function per kernel family (run-time facts -> instantiation + geometry), ONE launch_kernel, ONE resident_workgroups, the entry points.
 //
 // One workgroup = one wavefront = ROWS QPs (one per main / twin pair of 16-lane DPP rows; ROWS = 2 at H = 10, 1 at H >= 16), dynamic LDS =
 // ROWS x Layout<H>::ROW_STRIDE doubles (20.4 KB per QP at H = 10 -> eight QPs = four workgroups per CU); at H = 16 the persistent ADMM kernel is ONE
@@ -140,11 +141,7 @@ __global__ __launch_bounds__(64, WAVES) void a1mpc_setup_kernel(const KernelArgs
     setup_row<H, false, UPD>(a, tabl, b, a1mpc_lds + row * LayoutSetup<H>::ROW_STRIDE, prep);
 }
 // K2: persistent rows; grid = resident workgroups; every row drains the queue of prepared QPs.
-#ifdef A1X_NOTWIN
-constexpr bool admm_twin_rows(int, int) { return false; }
-#else
-constexpr bool admm_twin_rows(int h, int rows) { return twin_rows(h, kModeMpc, rows); }
-#endif  // the wavefront's spare rows run as twins (RowSolver<.., TWIN>)
+constexpr bool admm_twin_rows(int h, int rows) { return twin_rows(h, kModeMpc, rows); }  // the wavefront's spare rows run as twins (RowSolver<.., TWIN>)
 // UPD: the instantiation that also serves warm_start = 2 (the reference's update path); every other mode runs UPD = false, whose code is what it was before
 // the update path existed (the allocation of the hot loop is sensitive to anything around it: a1mpc_solver.hpp, load_prepared)
 // UNI: contacts broadcast over the horizon (contact_stride = 0): one pair of bounds for every slot (RowSolver<.., UNI>; built for H >= 16, where the registers matter)
@@ -246,75 +243,150 @@ __global__ __launch_bounds__(256) void a1mpc_admm_gen_cu_kernel(const KernelArgs
 }
 
 
-// workgroups of the persistent ADMM kernel that are resident at once on the current device (occupancy query, cached per device)
+// ---- host side: select an instantiation, launch it ---------------------------------------------------------------
+// One instantiation of a kernel family and the geometry it is launched with (what the select_* functions return); clk: a profiling instantiation, whose launch sets g_clk_ran
+template <class... P>
+struct Kernel { void (*fn)(P...); Geometry g; bool clk = false; };
+using SolveKernel = Kernel<KernelArgs>;                       // fused and latency kernels: inputs to outputs
+using SetupKernel = Kernel<KernelArgs, double*>;              // K1 of a split pipeline
+using AdmmKernel = Kernel<KernelArgs, const double*, int*>;   // K2: persistent rows on the queue
+
+// THE launch of a solver kernel: the dynamic-LDS limit (first time on this device), the launch, the error check.  dev: the current device -- a launch function asks for it
+// once (hipGetDevice) and hands it to every call below
+template <class... P, class... A>
+static a1mpc_status launch_kernel(int dev, const Kernel<P...>& k, int64_t grid, hipStream_t stream, const A&... args) {
+    if (a1mpc_status st = set_lds_attr(dev, reinterpret_cast<const void*>(k.fn), k.g.lds); st != A1MPC_OK) return st;
+    hipLaunchKernelGGL(k.fn, dim3(static_cast<unsigned>(grid)), dim3(static_cast<unsigned>(k.g.threads)), k.g.lds, stream, args...);
+    A1_HIP(hipGetLastError());
+    if (k.clk) g_clk_ran = true;
+    return A1MPC_OK;
+}
+// workgroups of a persistent kernel that are resident at once on the current device
+template <class... P>
+static a1mpc_status resident_workgroups(int dev, const Kernel<P...>& k, int* out) {
+    return resident_workgroups(dev, reinterpret_cast<const void*>(k.fn), k.g.threads, k.g.lds, out);
+}
+inline int64_t workgroups_for(int64_t n, const Geometry& g) { return (n + g.qps - 1) / g.qps; }
+
+// The run-time facts of a launch that pick an instantiation: upd = warm_start = 2 (the update path, a.carry), bc = contacts broadcast over the horizon (contact_stride = 0),
+// clk = profiling (a1mpc_set_profiling, a.clk).  The `if constexpr` guards are which instantiations exist (every extra one of H = 16 / 20 costs a minute of build).
+template <int H>
+static SetupKernel select_setup(bool upd) {
+    const Geometry g{64, 4, sizeof(double) * (4 * LayoutSetup<H>::ROW_STRIDE + 2 * H * H)};
+    if constexpr (H > 1) { if (upd) return {&a1mpc_setup_kernel<H, 1, true>, g}; }   // (same resources, a few more instructions around set-up and iteration 1)
+    return {&a1mpc_setup_kernel<H, 1>, g};
+}
+// five QPs per CU (H = 16, unless A1MPC_CU_WIDE=0).  A1MPC_CU_QUAD=0 reaches the broadcast-contact kernel only
+template <int H>
+static AdmmKernel select_admm_cu(bool upd, bool bc, bool clk) {
+    constexpr Geometry g = admm_geometry<H>(true);
+    if (clk && !upd && bc) return {&a1mpc_admm_cu_kernel<H, false, true, true, true>, g, true};   // (the profiling instantiation of the kernel broadcast contacts run)
+    if (upd) return {&a1mpc_admm_cu_kernel<H, true, false, false, true>, g};
+    if (bc && cu_quad_enabled()) return {&a1mpc_admm_cu_kernel<H, false, true, false, true>, g};
+    if (bc) return {&a1mpc_admm_cu_kernel<H, false, true>, g};
+    return {&a1mpc_admm_cu_kernel<H, false, false, false, true>, g};
+}
+// one wavefront of R QPs; (false, false, false) is the base instantiation, whose residency decides between the pipelines (resident_rows)
+template <int H>
+static AdmmKernel select_admm_rows(bool upd, bool bc, bool clk) {
+    constexpr int R = default_rows_per_wg(H);
+    constexpr bool Q = quad_rows(H, R);
+    constexpr Geometry g = admm_geometry<H>(false);
+    if constexpr (H > 1) { if (upd) return {&a1mpc_admm_kernel<H, R, true, false, false, Q>, g}; }
+    if constexpr (H > 1 && cu_wide_qps(H) == 0) {   // the kernel of the default batches with clock stamps
+        if (clk && bc) return {&a1mpc_admm_kernel<H, R, false, H >= 16, true, Q>, g, true};
+    }
+    if constexpr (H >= 16) {   // broadcast contacts: one pair of bounds for all slots (UNI); H = 20: a quad of rows unless A1MPC_QUAD=0
+        if constexpr (Q) { if (bc && quad_enabled()) return {&a1mpc_admm_kernel<H, R, false, true, false, true>, g}; }
+        if (bc) return {&a1mpc_admm_kernel<H, R, false, true>, g};
+    }
+    return {&a1mpc_admm_kernel<H, R, false, false, false, Q>, g};
+}
+template <int H>
+static AdmmKernel select_admm(bool upd, bool bc, bool clk) {
+    if constexpr (cu_wide_qps(H) > 0) { if (cu_wide_enabled()) return select_admm_cu<H>(upd, bc, clk); }
+    return select_admm_rows<H>(upd, bc, clk);
+}
+// fused kernel; profiling instantiations (stage stamps of the whole tick, both warm-start semantics) at tick_clk_horizon only
+template <int H, int MODE>
+static SolveKernel select_fused(bool upd, bool bc, bool clk) {
+    constexpr int R = default_rows_per_wg(H);
+    const SolveKernel base{&a1mpc_solve_kernel<H, MODE, R>, {twin_rows(H, MODE, R) ? 64 : 16 * R, R, lds_bytes<H>(R)}};
+    const Geometry g = base.g;
+    if constexpr (MODE == kModeMpc && tick_clk_horizon(H)) {
+        if (clk && bc && upd) return {&a1mpc_solve_kernel<H, MODE, R, true, true>, g, true};
+        if (clk && bc) return {&a1mpc_solve_kernel<H, MODE, R, false, true>, g, true};
+    }
+    if constexpr (MODE == kModeMpc && H > 1) { if (upd) return {&a1mpc_solve_kernel<H, MODE, R, true>, g}; }
+    return base;
+}
+// latency kernel (H > 1, MPC): one wavefront per QP
+template <int H>
+static SolveKernel select_coop(bool upd, bool bc, bool clk) {
+    const SolveKernel base{&a1mpc_solve_coop_kernel<H>, {64, 1, lds_bytes<H>(1)}};
+    const Geometry g = base.g;
+    if constexpr (tick_clk_horizon(H)) {
+        if (clk && bc && upd) return {&a1mpc_solve_coop_kernel<H, true, true>, g, true};
+        if (clk && bc) return {&a1mpc_solve_coop_kernel<H, false, true>, g, true};
+    }
+    if (upd) return {&a1mpc_solve_coop_kernel<H, true>, g};
+    return base;
+}
+// general path, fused: a handful of QPs at a horizon without quads of rows take its latency kernel (one wavefront per QP, its four rows share the set-up)
 template <int H, int ROWS>
-static a1mpc_status resident_workgroups(int* out) {
-    static int resident[64] = {};
-    int dev = 0;
-    A1_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { *out = 512; return A1MPC_OK; }
-    std::lock_guard<std::mutex> lock(g_cache_mu);
-    if (!resident[dev]) {
-        const size_t lds2 = lds_bytes<H>(ROWS);
-        A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_admm_kernel<H, ROWS, false, false, false, quad_rows(H, ROWS)>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(lds2)));
-        int per_cu = 0, cus = 0;
-        A1_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&a1mpc_admm_kernel<H, ROWS, false, false, false, quad_rows(H, ROWS)>), admm_twin_rows(H, ROWS) ? 64 : 16 * ROWS, lds2));
-        A1_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        resident[dev] = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+static SolveKernel select_gen(bool upd, int64_t n) {
+    if constexpr (H % 4 != 0) {
+        if (n <= coop_max_batch() && coop_setup_enabled()) {
+            constexpr Geometry g{64, 1, sizeof(double) * Layout<H, true>::ROW_STRIDE};
+            if (upd) return {&a1mpc_solve_gen_coop_kernel<H, true>, g};
+            return {&a1mpc_solve_gen_coop_kernel<H, false>, g};
+        }
     }
-    *out = resident[dev];
-    return A1MPC_OK;
+    const SolveKernel base{&a1mpc_solve_gen_kernel<H, ROWS>, {64, ROWS, sizeof(double) * ROWS * Layout<H, true>::ROW_STRIDE}};
+    if (upd) return {&a1mpc_solve_gen_kernel<H, ROWS, true>, base.g};
+    return base;
 }
+// general path, split pipeline
 template <int H>
-static a1mpc_status resident_cu_workgroups(int* out) {
-    static int resident[64] = {};
-    int dev = 0;
-    A1_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { *out = 256; return A1MPC_OK; }
-    std::lock_guard<std::mutex> lock(g_cache_mu);
-    if (!resident[dev]) {
-        const size_t lds2 = lds_bytes<H>(cu_wide_qps(H));
-        A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_admm_cu_kernel<H, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds2)));
-        int per_cu = 0, cus = 0;
-        A1_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&a1mpc_admm_cu_kernel<H, false, false, false, true>), 256, lds2));
-        A1_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        resident[dev] = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    }
-    *out = resident[dev];
-    return A1MPC_OK;
+static SetupKernel select_setup_gen() {
+    constexpr int QPW = 4 / setup_gen_rows(H);   // QPs per wavefront of the set-up kernel
+    return {&a1mpc_setup_gen_kernel<H>, {64, QPW, sizeof(double) * (QPW * LayoutSetup<H, true>::ROW_STRIDE + 2 * H * H)}};
 }
-template <int H>
-a1mpc_status resident_rows(int* out) {
-    int wg = 0;
-    a1mpc_status st;
-#ifdef A1MPC_ALL_ROWS
-    switch (rows_per_wg(H)) {
-        case 1: st = resident_workgroups<H, 1>(&wg); *out = wg; return st;
-        case 2: st = resident_workgroups<H, 2>(&wg); *out = 2 * wg; return st;
+template <int H, int ROWS>
+static AdmmKernel select_admm_gen_rows() { return {&a1mpc_admm_gen_kernel<H, ROWS>, {64, ROWS, sizeof(double) * ROWS * Layout<H, true>::ROW_STRIDE}}; }
+template <int H, int ROWS>
+static AdmmKernel select_admm_gen() {
+    if constexpr (cu_wide_gen_qps(H) > 0) {   // seven QPs per CU: one 256-thread workgroup per CU; a slot of a two-slot pipeline keeps the one-wave workgroups
+        constexpr int Q = cu_wide_gen_qps(H);
+        if (gen_cu_wide_enabled() && !g_gen_prefer_one_wave) return {&a1mpc_admm_gen_cu_kernel<H>, {256, Q, sizeof(double) * Q * Layout<H, true>::ROW_STRIDE}};
     }
-    st = resident_workgroups<H, 4>(&wg); *out = 4 * wg;
-#else
-    st = resident_workgroups<H, default_rows_per_wg(H)>(&wg); *out = default_rows_per_wg(H) * wg;
-#endif
-    return st;
+    return select_admm_gen_rows<H, ROWS>();
 }
 
-template <int H, int ROWS>
-static a1mpc_status launch_split_rows(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid) {
-    const size_t lds2 = lds_bytes<H>(ROWS), lds1 = sizeof(double) * (4 * LayoutSetup<H>::ROW_STRIDE + 2 * H * H);
-    int res = 0;
-    if (a1mpc_status st = resident_workgroups<H, ROWS>(&res); st != A1MPC_OK) return st;
+// ---- the entry points (declared in a1mpc_common.hpp)
+// rows of the one-wave persistent kernel that are resident at once: a batch beyond them takes the split pipeline (a1mpc_hip.hip, use_split_pipeline)
+template <int H>
+a1mpc_status resident_rows(int* out) {
+    int dev = 0, wg = 0;
+    A1_HIP(hipGetDevice(&dev));
+    const AdmmKernel k = select_admm_rows<H>(false, false, false);
+    const a1mpc_status st = resident_workgroups(dev, k, &wg);
+    *out = k.g.qps * wg;
+    return st;
+}
+template <int H>
+a1mpc_status launch_split(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid) {
+    int dev = 0, res = 0;
+    A1_HIP(hipGetDevice(&dev));
+    const bool upd = a.carry != nullptr, bc = a.contact_stride == 0;
+    const SetupKernel k1 = select_setup<H>(upd);
+    const AdmmKernel k2 = select_admm<H>(upd, bc, a.clk != nullptr);
+    if (a1mpc_status st = resident_workgroups(dev, select_admm<H>(false, false, false), &res); st != A1MPC_OK) return st;   // (of the family's base instantiation: one query per device)
     A1_HIP(hipMemsetAsync(counter, 0, sizeof(int), stream));
-    bool upd_kernels = false;   // warm_start = 2: the update-path instantiations of the two kernels (H > 1, default rows per workgroup; same resources, a few more instructions around set-up and iteration 1)
-    constexpr bool kHasUpd = H > 1 && ROWS == default_rows_per_wg(H);
-    if constexpr (kHasUpd) upd_kernels = a.carry != nullptr;
     {
         RoctxRange range("a1mpc set-up");
-        if constexpr (kHasUpd) { if (upd_kernels) hipLaunchKernelGGL((a1mpc_setup_kernel<H, 1, true>), dim3(static_cast<unsigned>((a.n + 3) / 4)), dim3(64), lds1, stream, a, prep); }
-        if (!upd_kernels) hipLaunchKernelGGL((a1mpc_setup_kernel<H, 1>), dim3(static_cast<unsigned>((a.n + 3) / 4)), dim3(64), lds1, stream, a, prep);
+        if (a1mpc_status st = launch_kernel(dev, k1, workgroups_for(a.n, k1.g), stream, a, prep); st != A1MPC_OK) return st;
     }
-    A1_HIP(hipGetLastError());
     // queue order of THIS solve, longest first: by the set-up kernel's cost guesses (predict: no history) or by the cost each QP had in the handle's previous
     // solve of this batch size (the cost buffer still holds it; the ADMM kernel below overwrites it with this solve's).  Sorted here, in front of the kernel
     // that needs it, not behind the solve that produced the costs: a one-workgroup kernel of 1024 threads behind a persistent kernel waits for a free CU, and
@@ -326,289 +398,51 @@ static a1mpc_status launch_split_rows(const KernelArgs& a, double* prep, int* co
     }
     if (mid) A1_HIP(hipEventRecord(mid, stream));  // stage split: formation + Ruiz (+ queue order) | factor + iterate
     RoctxRange range_admm("a1mpc admm");
-    if constexpr (cu_wide_qps(H) > 0 && ROWS == default_rows_per_wg(H)) {
-        if (cu_wide_enabled()) {   // five QPs per CU: one 256-thread workgroup per CU (a1mpc_admm_cu_kernel)
-            constexpr int Q = cu_wide_qps(H);
-            const size_t ldsq = lds_bytes<H>(Q);
-            int resq = 0;
-            if (a1mpc_status st = resident_cu_workgroups<H>(&resq); st != A1MPC_OK) return st;
-            const int wantq = (a.n + Q - 1) / Q;
-            const dim3 gridq(static_cast<unsigned>(wantq < resq ? wantq : resq)), blockq(256);
-            if (a.clk != nullptr && a.carry == nullptr && a.contact_stride == 0) {   // profiling instantiation (of the kernel broadcast contacts run)
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_cu_kernel<H, false, true, true, true>), ldsq); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_admm_cu_kernel<H, false, true, true, true>), gridq, blockq, ldsq, stream, a, static_cast<const double*>(prep), counter);
-                g_clk_ran = true;
-            } else if (a.carry != nullptr) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_cu_kernel<H, true, false, false, true>), ldsq); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_admm_cu_kernel<H, true, false, false, true>), gridq, blockq, ldsq, stream, a, static_cast<const double*>(prep), counter);
-            } else if (a.contact_stride == 0 && cu_quad_enabled()) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_cu_kernel<H, false, true, false, true>), ldsq); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_admm_cu_kernel<H, false, true, false, true>), gridq, blockq, ldsq, stream, a, static_cast<const double*>(prep), counter);
-            } else if (a.contact_stride == 0) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_cu_kernel<H, false, true>), ldsq); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_admm_cu_kernel<H, false, true>), gridq, blockq, ldsq, stream, a, static_cast<const double*>(prep), counter);
-            } else {
-                hipLaunchKernelGGL((a1mpc_admm_cu_kernel<H, false, false, false, true>), gridq, blockq, ldsq, stream, a, static_cast<const double*>(prep), counter);
-            }
-            A1_HIP(hipGetLastError());
-            return A1MPC_OK;
-        }
-    }
-    const int want = (a.n + ROWS - 1) / ROWS;
-    const dim3 grid(static_cast<unsigned>(want < res ? want : res)), block(admm_twin_rows(H, ROWS) ? 64 : 16 * ROWS);
-    if constexpr (kHasUpd) {
-        if (upd_kernels) {
-            if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_kernel<H, ROWS, true, false, false, quad_rows(H, ROWS)>), lds2); st != A1MPC_OK) return st;
-            hipLaunchKernelGGL((a1mpc_admm_kernel<H, ROWS, true, false, false, quad_rows(H, ROWS)>), grid, block, lds2, stream, a, static_cast<const double*>(prep), counter);
-        }
-    }
-    // profiling instantiation (a1mpc_set_profiling; H > 1, default rows, no update path, broadcast contacts): the kernel of the default batches with clock stamps
-    if constexpr (H > 1 && ROWS == default_rows_per_wg(H) && admm_twin_rows(H, ROWS) && cu_wide_qps(H) == 0) {
-        if (a.clk != nullptr && !upd_kernels && a.contact_stride == 0) {
-            constexpr bool kUni = H >= 16;
-            if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_kernel<H, ROWS, false, kUni, true, quad_rows(H, ROWS)>), lds2); st != A1MPC_OK) return st;
-            hipLaunchKernelGGL((a1mpc_admm_kernel<H, ROWS, false, kUni, true, quad_rows(H, ROWS)>), grid, block, lds2, stream, a, static_cast<const double*>(prep), counter);
-            A1_HIP(hipGetLastError());
-            g_clk_ran = true;
-            return A1MPC_OK;
-        }
-    }
-    bool uni_kernel = false;   // broadcast contacts at H >= 16: the instantiation with one pair of bounds for all slots
-    constexpr bool kHasUni = H >= 16 && ROWS == default_rows_per_wg(H) && admm_twin_rows(H, ROWS);
-    if constexpr (kHasUni) {
-        uni_kernel = !upd_kernels && a.contact_stride == 0;
-        bool quad = false;
-        if constexpr (quad_rows(H, ROWS)) quad = uni_kernel && quad_enabled();
-        if constexpr (quad_rows(H, ROWS)) {
-            if (quad) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_kernel<H, ROWS, false, true, false, true>), lds2); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_admm_kernel<H, ROWS, false, true, false, true>), grid, block, lds2, stream, a, static_cast<const double*>(prep), counter);
-            }
-        }
-        if (uni_kernel && !quad) {
-            if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_admm_kernel<H, ROWS, false, true>), lds2); st != A1MPC_OK) return st;
-            hipLaunchKernelGGL((a1mpc_admm_kernel<H, ROWS, false, true>), grid, block, lds2, stream, a, static_cast<const double*>(prep), counter);
-        }
-    }
-    if (!upd_kernels && !uni_kernel) hipLaunchKernelGGL((a1mpc_admm_kernel<H, ROWS, false, false, false, quad_rows(H, ROWS)>), grid, block, lds2, stream, a, static_cast<const double*>(prep), counter);
-    A1_HIP(hipGetLastError());
-    return A1MPC_OK;
+    const int64_t want = workgroups_for(a.n, k2.g);
+    return launch_kernel(dev, k2, want < res ? want : res, stream, a, static_cast<const double*>(prep), counter);
 }
-template <int H>
-a1mpc_status launch_split(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid) {
-#ifdef A1MPC_ALL_ROWS
-    if (a.carry == nullptr) {   // (the update-path kernels exist for the default rows per workgroup only)
-        switch (rows_per_wg(H)) {
-            case 1: return launch_split_rows<H, 1>(a, prep, counter, stream, mid);
-            case 2: return launch_split_rows<H, 2>(a, prep, counter, stream, mid);
-        }
-        return launch_split_rows<H, 4>(a, prep, counter, stream, mid);
-    }
-#endif
-    return launch_split_rows<H, default_rows_per_wg(H)>(a, prep, counter, stream, mid);
-}
-
-template <int H, int MODE, int ROWS>
-static a1mpc_status launch_rows(const KernelArgs& a, hipStream_t stream) {
-    static bool attr_set[64] = {};
+template <int H, int MODE>
+a1mpc_status launch(const KernelArgs& a, hipStream_t stream) {
     int dev = 0;
     A1_HIP(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mu);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_solve_kernel<H, MODE, ROWS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes<H>(ROWS))));
-            attr_set[dev] = true;
-        }
+    const bool upd = a.carry != nullptr, bc = a.contact_stride == 0, clk = a.clk != nullptr;
+    if constexpr (MODE == kModeMpc && H > 1) {
+        if (coop_setup_enabled() && a.n <= coop_max_batch()) return launch_kernel(dev, select_coop<H>(upd, bc, clk), a.n, stream, a);
     }
-    const unsigned grid = static_cast<unsigned>((a.n + ROWS - 1) / ROWS);
-    if constexpr (MODE == kModeMpc && tick_clk_horizon(H) && ROWS == default_rows_per_wg(H)) {
-        if (a.clk != nullptr && a.contact_stride == 0) {   // profiling instantiations (a1mpc_set_profiling): stage stamps of the whole tick, both warm-start semantics
-            const dim3 blk(twin_rows(H, MODE, ROWS) ? 64 : 16 * ROWS);
-            if (a.carry != nullptr) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_kernel<H, MODE, ROWS, true, true>), lds_bytes<H>(ROWS)); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_solve_kernel<H, MODE, ROWS, true, true>), dim3(grid), blk, lds_bytes<H>(ROWS), stream, a);
-            } else {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_kernel<H, MODE, ROWS, false, true>), lds_bytes<H>(ROWS)); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_solve_kernel<H, MODE, ROWS, false, true>), dim3(grid), blk, lds_bytes<H>(ROWS), stream, a);
-            }
-            A1_HIP(hipGetLastError());
-            g_clk_ran = true;
-            return A1MPC_OK;
-        }
-    }
-    if constexpr (MODE == kModeMpc && H > 1 && ROWS == default_rows_per_wg(H)) {
-        if (a.carry != nullptr) {   // warm_start = 2: the update-path instantiation
-            if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_kernel<H, MODE, ROWS, true>), lds_bytes<H>(ROWS)); st != A1MPC_OK) return st;
-            hipLaunchKernelGGL((a1mpc_solve_kernel<H, MODE, ROWS, true>), dim3(grid), dim3(twin_rows(H, MODE, ROWS) ? 64 : 16 * ROWS), lds_bytes<H>(ROWS), stream, a);
-            A1_HIP(hipGetLastError());
-            return A1MPC_OK;
-        }
-    }
-    hipLaunchKernelGGL((a1mpc_solve_kernel<H, MODE, ROWS>), dim3(grid), dim3(twin_rows(H, MODE, ROWS) ? 64 : 16 * ROWS), lds_bytes<H>(ROWS), stream, a);
-    A1_HIP(hipGetLastError());
-    return A1MPC_OK;
+    const SolveKernel k = select_fused<H, MODE>(upd, bc, clk);
+    return launch_kernel(dev, k, workgroups_for(a.n, k.g), stream, a);
 }
 template <int H, int ROWS>
 a1mpc_status launch_gen_rows(const KernelArgs& a, hipStream_t stream) {
-    static bool attr_set[64] = {};
     int dev = 0;
     A1_HIP(hipGetDevice(&dev));
-    if constexpr (H % 4 != 0) {   // a handful of QPs at H = 10: one wavefront per QP, its four rows share the set-up (a1mpc_solve_gen_coop_kernel)
-        if (a.n <= coop_max_batch() && coop_setup_enabled()) {
-            const size_t lds1 = sizeof(double) * Layout<H, true>::ROW_STRIDE;
-            if (a.carry != nullptr) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_gen_coop_kernel<H, true>), lds1); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_solve_gen_coop_kernel<H, true>), dim3(static_cast<unsigned>(a.n)), dim3(64), lds1, stream, a);
-            } else {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_gen_coop_kernel<H, false>), lds1); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_solve_gen_coop_kernel<H, false>), dim3(static_cast<unsigned>(a.n)), dim3(64), lds1, stream, a);
-            }
-            A1_HIP(hipGetLastError());
-            return A1MPC_OK;
-        }
-    }
-    const size_t lds = sizeof(double) * ROWS * Layout<H, true>::ROW_STRIDE;
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mu);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_solve_gen_kernel<H, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds)));
-            attr_set[dev] = true;
-        }
-    }
-    if (a.carry != nullptr) {   // warm_start = 2: the update-path instantiation
-        if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_gen_kernel<H, ROWS, true>), lds); st != A1MPC_OK) return st;
-        hipLaunchKernelGGL((a1mpc_solve_gen_kernel<H, ROWS, true>), dim3(static_cast<unsigned>((a.n + ROWS - 1) / ROWS)), dim3(64), lds, stream, a);
-        A1_HIP(hipGetLastError());
-        return A1MPC_OK;
-    }
-    hipLaunchKernelGGL((a1mpc_solve_gen_kernel<H, ROWS>), dim3(static_cast<unsigned>((a.n + ROWS - 1) / ROWS)), dim3(64), lds, stream, a);
-    A1_HIP(hipGetLastError());
-    return A1MPC_OK;
+    const SolveKernel k = select_gen<H, ROWS>(a.carry != nullptr, a.n);
+    return launch_kernel(dev, k, workgroups_for(a.n, k.g), stream, a);
 }
-// resident workgroups of the general path's ADMM kernel (occupancy query, cached per device)
+// resident workgroups of the general path's one-wave ADMM kernel: a batch beyond their rows takes the general path's split pipeline (a1mpc_hip.hip, solve_device_impl)
 template <int H, int ROWS>
 a1mpc_status resident_workgroups_gen(int* out) {
-    static int resident[64] = {};
     int dev = 0;
     A1_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(A1MPC_ERR_HIP, "device index out of range");
-    std::lock_guard<std::mutex> lock(g_cache_mu);
-    if (!resident[dev]) {
-        const size_t lds = sizeof(double) * ROWS * Layout<H, true>::ROW_STRIDE;
-        A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_admm_gen_kernel<H, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        int per_cu = 0, cus = 0;
-        A1_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&a1mpc_admm_gen_kernel<H, ROWS>), 64, lds));
-        A1_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        resident[dev] = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    }
-    *out = resident[dev];
-    return A1MPC_OK;
+    return resident_workgroups(dev, select_admm_gen_rows<H, ROWS>(), out);
 }
 // a batch beyond the resident rows: the general path's set-up kernel, the queue-order kernel, its persistent ADMM kernel
 template <int H, int ROWS>
-a1mpc_status launch_gen_split_rows(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid, int res) {
-    static bool attr_set[64] = {};
-    int dev = 0;
+a1mpc_status launch_gen_split_rows(const KernelArgs& a, double* prep, int* counter, hipStream_t stream, hipEvent_t mid) {
+    int dev = 0, res = 0;
     A1_HIP(hipGetDevice(&dev));
-    constexpr int QPW = 4 / setup_gen_rows(H);   // QPs per wavefront of the set-up kernel
-    const size_t lds1 = sizeof(double) * (QPW * LayoutSetup<H, true>::ROW_STRIDE + 2 * H * H), lds2 = sizeof(double) * ROWS * Layout<H, true>::ROW_STRIDE;
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mu);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_setup_gen_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds1)));
-            attr_set[dev] = true;
-        }
-    }
+    const SetupKernel k1 = select_setup_gen<H>();
+    const AdmmKernel k2 = select_admm_gen<H, ROWS>();
+    if (a1mpc_status st = resident_workgroups(dev, k2, &res); st != A1MPC_OK) return st;
     A1_HIP(hipMemsetAsync(counter, 0, sizeof(int), stream));
-    hipLaunchKernelGGL((a1mpc_setup_gen_kernel<H>), dim3(static_cast<unsigned>((a.n + QPW - 1) / QPW)), dim3(64), lds1, stream, a, prep);
-    A1_HIP(hipGetLastError());
-    if (a.cost != nullptr && a.order != nullptr) {   // (predicted or the previous solve's costs: see launch_split_rows)
+    if (a1mpc_status st = launch_kernel(dev, k1, workgroups_for(a.n, k1.g), stream, a, prep); st != A1MPC_OK) return st;
+    if (a.cost != nullptr && a.order != nullptr) {   // (predicted or the previous solve's costs: see launch_split)
         launch_order_kernel(static_cast<int>(a.n), static_cast<const int32_t*>(a.cost), const_cast<int32_t*>(a.order), stream);
         A1_HIP(hipGetLastError());
     }
     if (mid) A1_HIP(hipEventRecord(mid, stream));
-    if constexpr (cu_wide_gen_qps(H) > 0) {
-        if (gen_cu_wide_enabled() && !g_gen_prefer_one_wave) {   // seven QPs per CU: one 256-thread workgroup per CU (a1mpc_admm_gen_cu_kernel); a slot of a two-slot pipeline keeps the one-wave workgroups
-            constexpr int Q = cu_wide_gen_qps(H);
-            const size_t ldsq = sizeof(double) * Q * Layout<H, true>::ROW_STRIDE;
-            static int resq_dev[64] = {};
-            int resq = 0;
-            {
-                std::lock_guard<std::mutex> lock(g_cache_mu);
-                if (dev >= 0 && dev < 64 && !resq_dev[dev]) {
-                    A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_admm_gen_cu_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsq)));
-                    int per_cu = 0, cus = 0;
-                    A1_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&a1mpc_admm_gen_cu_kernel<H>), 256, ldsq));
-                    A1_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-                    resq_dev[dev] = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-                }
-                resq = (dev >= 0 && dev < 64) ? resq_dev[dev] : 256;
-            }
-            const int wantq = (a.n + Q - 1) / Q;
-            hipLaunchKernelGGL((a1mpc_admm_gen_cu_kernel<H>), dim3(static_cast<unsigned>(wantq < resq ? wantq : resq)), dim3(256), ldsq, stream, a, static_cast<const double*>(prep), counter);
-            A1_HIP(hipGetLastError());
-            return A1MPC_OK;
-        }
-    }
-    const int want = (a.n + ROWS - 1) / ROWS;
-    hipLaunchKernelGGL((a1mpc_admm_gen_kernel<H, ROWS>), dim3(static_cast<unsigned>(want < res ? want : res)), dim3(64), lds2, stream, a, static_cast<const double*>(prep), counter);
-    A1_HIP(hipGetLastError());
-    return A1MPC_OK;
-}
-template <int H>
-static a1mpc_status launch_coop(const KernelArgs& a, hipStream_t stream) {
-    static bool attr_set[64] = {};
-    int dev = 0;
-    A1_HIP(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mu);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            A1_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&a1mpc_solve_coop_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds_bytes<H>(1))));
-            attr_set[dev] = true;
-        }
-    }
-    if constexpr (tick_clk_horizon(H)) {
-        if (a.clk != nullptr && a.contact_stride == 0) {   // profiling instantiations (a1mpc_set_profiling)
-            if (a.carry != nullptr) {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_coop_kernel<H, true, true>), lds_bytes<H>(1)); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_solve_coop_kernel<H, true, true>), dim3(static_cast<unsigned>(a.n)), dim3(64), lds_bytes<H>(1), stream, a);
-            } else {
-                if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_coop_kernel<H, false, true>), lds_bytes<H>(1)); st != A1MPC_OK) return st;
-                hipLaunchKernelGGL((a1mpc_solve_coop_kernel<H, false, true>), dim3(static_cast<unsigned>(a.n)), dim3(64), lds_bytes<H>(1), stream, a);
-            }
-            A1_HIP(hipGetLastError());
-            g_clk_ran = true;
-            return A1MPC_OK;
-        }
-    }
-    if (a.carry != nullptr) {   // warm_start = 2: the update-path instantiation
-        if (a1mpc_status st = set_lds_attr(reinterpret_cast<const void*>(&a1mpc_solve_coop_kernel<H, true>), lds_bytes<H>(1)); st != A1MPC_OK) return st;
-        hipLaunchKernelGGL((a1mpc_solve_coop_kernel<H, true>), dim3(static_cast<unsigned>(a.n)), dim3(64), lds_bytes<H>(1), stream, a);
-        A1_HIP(hipGetLastError());
-        return A1MPC_OK;
-    }
-    hipLaunchKernelGGL((a1mpc_solve_coop_kernel<H>), dim3(static_cast<unsigned>(a.n)), dim3(64), lds_bytes<H>(1), stream, a);
-    A1_HIP(hipGetLastError());
-    return A1MPC_OK;
-}
-template <int H, int MODE>
-a1mpc_status launch(const KernelArgs& a, hipStream_t stream) {
-    if constexpr (MODE == kModeMpc && H > 1) {
-        if (coop_setup_enabled() && a.n <= coop_max_batch()) return launch_coop<H>(a, stream);
-    }
-#ifdef A1MPC_ALL_ROWS
-    if (a.carry == nullptr) {   // (the update-path kernels exist for the default rows per workgroup only)
-        switch (rows_per_wg(H)) {
-            case 1: return launch_rows<H, MODE, 1>(a, stream);
-            case 2: return launch_rows<H, MODE, 2>(a, stream);
-        }
-        return launch_rows<H, MODE, 4>(a, stream);
-    }
-#endif
-    return launch_rows<H, MODE, default_rows_per_wg(H)>(a, stream);
+    const int64_t want = workgroups_for(a.n, k2.g);
+    return launch_kernel(dev, k2, want < res ? want : res, stream, a, static_cast<const double*>(prep), counter);
 }
 
 }  // namespace a1mpc

@@ -385,3 +385,30 @@ def test_quad_of_rows_kernels_leave_the_twin_pairs_bits(pkg, h, n):
     assert r.returncode == 0, r.stdout[-800:] + r.stderr[-800:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
     assert res["bit_identical"] is True, r.stdout[-800:]
+
+
+# (QPs, threads, dynamic LDS bytes) per workgroup of the persistent ADMM kernel.  The LDS byte counts are what a1mpc_kernel_info of the library returned on an MI355X at
+# the commit before the launch layer took these numbers from the launch code's own geometry (they equal 8 x QPs x Layout<H>::ROW_STRIDE).
+KERNEL_INFO = {1: (2, 32, 5280), 10: (2, 64, 40704), 12: (2, 64, 48576), 16: (5, 256, 160880), 20: (1, 64, 40064)}
+KERNEL_INFO_H16_ONE_WAVE = (1, 64, 32176)   # A1MPC_CU_WIDE=0: the one-wave kernel, one QP (a main / twin pair of rows) per wavefront
+
+
+def test_kernel_info_matches_the_launched_geometry(pkg, scen):
+    """a1mpc_kernel_info reports the geometry the split pipeline's persistent kernel is launched with (one source: admm_geometry, csrc/a1mpc_common.hpp): every kernel
+    layout there is -- h = 1 (no twin rows), two QPs per wavefront, the CU-wide workgroup of h = 16, one QP per wavefront -- and, in a child process, h = 16 without the
+    CU-wide kernel.  No solve is needed."""
+    import json, os, subprocess, sys
+    def info(horizon):
+        sc = scen.config3_random_flat(nb=8, horizon=horizon)
+        with _engine(pkg, sc, 8) as eng:
+            k = eng.kernel_info()
+        return (k["qps_per_workgroup"], k["threads_per_workgroup"], k["lds_bytes_per_workgroup"])
+    for horizon, want in KERNEL_INFO.items():
+        assert info(horizon) == want, horizon
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child = ("import json, sys; sys.path.insert(0, sys.argv[1]); import __graft_entry__ as g; pkg = g.load_package(); sc = pkg.scenarios.config3_random_flat(nb=8, horizon=16)\n"
+             "with pkg.Engine(pkg.make_config(sc['params'], 16), max_batch=8, device=0) as eng: print(json.dumps(eng.kernel_info()))")
+    r = subprocess.run([sys.executable, "-c", child, root], capture_output=True, text=True, timeout=300, env=dict(os.environ, A1MPC_CU_WIDE="0"))
+    assert r.returncode == 0, r.stdout[-500:] + r.stderr[-500:]
+    k = json.loads(r.stdout.strip().splitlines()[-1])
+    assert (k["qps_per_workgroup"], k["threads_per_workgroup"], k["lds_bytes_per_workgroup"]) == KERNEL_INFO_H16_ONE_WAVE
