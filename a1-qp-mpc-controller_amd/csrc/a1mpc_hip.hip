@@ -784,6 +784,164 @@ __global__ __launch_bounds__(64) void a1mpc_plant_step_kernel(const PlantArgs a)
 #pragma unroll
     for (int mm = 0; mm < 3; ++mm) { const int e = lane + 64 * mm; if (e < cr) orr[e] = RL[e]; }
 }
+
+// ---- sensor synthesis (a1mpc_sensor_synthesis_batch): what a robot's sensors read on the plant above -- the inverse of the tick's front stages (quaternion -> R, leg
+// forward kinematics and Jacobian, the EKF's accelerometer and foot-velocity relations), so that  sensors -> tick -> plant -> sensors  closes on one stream.  The scheme is
+// stated in include/a1mpc.h and restated elementwise in tests/sensor_synthesis_ref.py.
+//   lanes     the plant step's: one wavefront = one workgroup = 16 consecutive robots, lane = 4 * (robot of the wave) + l; lane l holds leg l's lever, force and contact
+//             byte and does leg l's inverse kinematics.  The accelerometer's leg sum is pl_legs, (leg 0 + leg 1) + (leg 2 + leg 3).
+//   memory    state rows, R and the wrench pass through wave-private LDS in their memory layout; every global load is issued before the first operation.  The per-leg
+//             outputs are a lane's own words ([robot][12] doubles, [robot][4] doubles and bytes): written directly, once.  The per-robot outputs (quaternion, the two IMU
+//             vectors) are parked in LDS by lanes l of the robot (component l) and leave 64 consecutive doubles per instruction.
+//   bits      contraction off and no fma; +, -, *, / and sqrt are IEEE, atan2 / acos / sin / cos the device library's.
+//   dead lanes (robots >= n of the last wave) load the wave's first robot, take part in every shuffle and store nothing, neither to LDS nor to memory.
+struct SynthArgs {
+    int32_t n, stride;
+    double mass, rho_fix[20], rho_opt[12];
+    const double *state, *R, *foot, *grf, *ext;   // ext may be null
+    const uint8_t* contacts;
+    double *quat, *acc, *gyro, *jpos, *jvel, *fforce, *prel, *vrel;   // prel, vrel may be null
+    uint8_t* reach;
+};
+__global__ __launch_bounds__(64) void a1mpc_sensor_synthesis_kernel(const SynthArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double slds[kPlState + kPlR + kPlExt];
+    double* const S = slds; double* const RL = slds + kPlState; double* const E = slds + kPlState + kPlR;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, stride = a.stride;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    // every load, then the LDS writes, as in the plant step
+    const int cs = live * stride, cr = live * 9, ce = a.ext ? live * 6 : 0;
+    const double *gs = a.state + first * stride, *gr = a.R + first * 9, *ge = a.ext ? a.ext + first * 6 : a.R;
+    double vs[6], vr[3], ve[2];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; vs[m] = gs[e < cs ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vr[m] = gr[e < cr ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; ve[m] = ge[e < ce ? e : 0]; }
+    double r[3], f[3];
+    {
+        const double *fp = a.foot + b * 12 + 3 * l, *gp = a.grf + b * 12 + 3 * l;
+        r[0] = fp[0]; r[1] = fp[1]; r[2] = fp[2]; f[0] = gp[0]; f[1] = gp[1]; f[2] = gp[2];
+    }
+    const bool stance = a.contacts[b * 4 + l] != 0;
+    const double *gf = a.rho_fix + 5 * l, *go = a.rho_opt + 3 * l;
+    const double ox = gf[0], oy = gf[1], L = gf[2] + go[1], lt = gf[3], al = gf[4] - go[2], r0 = go[0];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; if (e < cs) S[e] = vs[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cr) RL[e] = vr[m]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; if (e < ce) E[e] = ve[m]; }
+    WaveStage::sync();
+    double w[3], v[3], R[9], fe[3] = {0.0, 0.0, 0.0};
+    {
+        const double* x = S + q * stride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { w[k] = x[6 + k]; v[k] = x[9 + k]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = RL[q * 9 + k];
+    }
+    const bool with_ext = a.ext != nullptr;
+    if (with_ext) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fe[k] = E[q * 6 + k];
+    }
+    const double m = a.mass;
+    // gyro = R^T omega; accelerometer = the specific force in the body frame: the stance legs' forces (a swing leg +0, selected) over m, plus R^T f_ext / m
+    double gyro[3], acc[3];
+    A1_PL_MTV(gyro, R, w);
+    {
+        double feb[3];
+        A1_PL_MTV(feb, R, fe);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[k] = pl_legs(stance ? f[k] : 0.0) / m;
+            if (with_ext) acc[k] = acc[k] + feb[k] / m;
+        }
+    }
+    const double ff = stance ? (R[6] * f[0] + R[7] * f[1]) + R[8] * f[2] : 0.0;   // the world z component of R f_l
+    // quaternion (w, x, y, z) of R: Eigen's matrix-to-quaternion, the four branches as selects of the operands around one sqrt
+    double qt[4];
+    {
+        const double tr = (R[0] + R[4]) + R[8];
+        const bool pos = tr > 0.0;
+        const int i = R[4] > R[0] ? (R[8] > R[4] ? 2 : 1) : (R[8] > R[0] ? 2 : 0);   // the largest diagonal: j = (i + 1) % 3, k = (j + 1) % 3
+        const double dii = pl_pick(i, R[0], R[4], R[8], 0.0), djj = pl_pick(i, R[4], R[8], R[0], 0.0), dkk = pl_pick(i, R[8], R[0], R[4], 0.0);
+        const double kj = pl_pick(i, R[7], R[2], R[3], 0.0), jk = pl_pick(i, R[5], R[6], R[1], 0.0);   // R(k, j), R(j, k)
+        const double ji = pl_pick(i, R[3], R[7], R[2], 0.0), ij = pl_pick(i, R[1], R[5], R[6], 0.0);
+        const double ki = pl_pick(i, R[6], R[1], R[5], 0.0), ik = pl_pick(i, R[2], R[3], R[7], 0.0);
+        const double t = sqrt(pos ? tr + 1.0 : ((dii - djj) - dkk) + 1.0), hq = 0.5 * t, u = 0.5 / t;
+        const double qi = hq, qw4 = (kj - jk) * u, qj = (ji + ij) * u, qk = (ki + ik) * u;
+        qt[0] = pos ? hq : qw4;
+        qt[1] = pos ? (R[7] - R[5]) * u : pl_pick(i, qi, qk, qj, 0.0);
+        qt[2] = pos ? (R[2] - R[6]) * u : pl_pick(i, qj, qi, qk, 0.0);
+        qt[3] = pos ? (R[3] - R[1]) * u : pl_pick(i, qk, qj, qi, 0.0);
+    }
+    // this leg: p = R^T r; the closed-form inverse of a1mpc_leg_kernel's forward map (knee bent back); bit 0 / bit 1 of reach = the hip / knee argument was clamped
+    double p[3], jq[3];
+    A1_PL_MTV(p, R, r);
+    const double dx = p[0] - ox, dy = p[1] - oy;
+    const double yz = dy * dy + p[2] * p[2], LL = L * L;
+    const bool clamp0 = yz < LL;
+    const double Zi = -sqrt(clamp0 ? 0.0 : yz - LL);
+    jq[0] = atan2(p[2], dy) - atan2(Zi, L);
+    const double ell = sqrt(al * al + r0 * r0), phi = atan2(r0, al);
+    const double cq = (((dx * dx + Zi * Zi) - lt * lt) - ell * ell) / ((2.0 * lt) * ell);
+    const bool clamp1 = cq < -1.0 || cq > 1.0;
+    const double kn = -acos(cq > 1.0 ? 1.0 : (cq < -1.0 ? -1.0 : cq));   // (a NaN stays a NaN)
+    jq[1] = atan2(-dx, -Zi) - atan2(ell * sin(kn), lt + ell * cos(kn));
+    jq[2] = kn + phi;
+    const int flags = (clamp0 ? 1 : 0) | (clamp1 ? 2 : 0);
+    // foot velocity in the body frame: a stance foot rests in the world, -(R^T (v + omega x r)); a swing foot rests in the body, +0
+    double fv[3];
+    {
+        const double u[3] = {v[0] + (w[1] * r[2] - w[2] * r[1]), v[1] + (w[2] * r[0] - w[0] * r[2]), v[2] + (w[0] * r[1] - w[1] * r[0])};
+        double ub[3];
+        A1_PL_MTV(ub, R, u);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fv[k] = stance ? -ub[k] : 0.0;
+    }
+    // joint rates: the leg kernel's Jacobian at the synthesised angles, inverted by cofactors like the plant's I_b^-1; exactly +0 where a reach bit is set
+    double jd[3];
+    {
+        const double s0 = sin(jq[0]), c0 = cos(jq[0]), s1 = sin(jq[1]), c1 = cos(jq[1]), s12 = sin(jq[1] + jq[2]), c12 = cos(jq[1] + jq[2]);
+        const double Xq = r0 * c12 - al * s12, Zq = -(al * c12) - r0 * s12;
+        const double Xr = Xq - lt * s1, Zp = Zq - lt * c1;
+        const double py = oy + (L * c0 - Zp * s0), pz = L * s0 + Zp * c0;
+        // row-major J: column c is d p / d q_c of the leg kernel (its J[3 c + row])
+        const double I[9] = {0.0, Zp, Zq, -pz, s0 * Xr, s0 * Xq, py - oy, -(c0 * Xr), -(c0 * Xq)};
+        const double c00 = I[4] * I[8] - I[5] * I[7], c01 = I[5] * I[6] - I[3] * I[8], c02 = I[3] * I[7] - I[4] * I[6];
+        const double id = 1.0 / ((I[0] * c00 + I[1] * c01) + I[2] * c02);
+        const double Ji[9] = {c00 * id, (I[2] * I[7] - I[1] * I[8]) * id, (I[1] * I[5] - I[2] * I[4]) * id,
+                              c01 * id, (I[0] * I[8] - I[2] * I[6]) * id, (I[2] * I[3] - I[0] * I[5]) * id,
+                              c02 * id, (I[1] * I[6] - I[0] * I[7]) * id, (I[0] * I[4] - I[1] * I[3]) * id};
+        A1_PL_MV(jd, Ji, fv);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) jd[k] = flags ? 0.0 : jd[k];
+    }
+    // out: a lane's own words directly; the per-robot vectors through the LDS images (every lane has read its inputs: sync first)
+    WaveStage::sync();
+    double* const QO = S; double* const AO = S + 64; double* const GO = S + 112;
+    if (alive) {
+        double *o0 = a.jpos + b * 12 + 3 * l, *o1 = a.jvel + b * 12 + 3 * l;
+        o0[0] = jq[0]; o0[1] = jq[1]; o0[2] = jq[2]; o1[0] = jd[0]; o1[1] = jd[1]; o1[2] = jd[2];
+        if (a.prel) { double* o = a.prel + b * 12 + 3 * l; o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; }
+        if (a.vrel) { double* o = a.vrel + b * 12 + 3 * l; o[0] = fv[0]; o[1] = fv[1]; o[2] = fv[2]; }
+        a.fforce[b * 4 + l] = ff;
+        a.reach[b * 4 + l] = static_cast<uint8_t>(flags);
+        QO[q * 4 + l] = pl_pick(l, qt[0], qt[1], qt[2], qt[3]);
+        if (l < 3) { AO[q * 3 + l] = pl_pick(l, acc[0], acc[1], acc[2], 0.0); GO[q * 3 + l] = pl_pick(l, gyro[0], gyro[1], gyro[2], 0.0); }
+    }
+    WaveStage::sync();
+    if (lane < live * 4) a.quat[first * 4 + lane] = QO[lane];
+    if (lane < live * 3) { a.acc[first * 3 + lane] = AO[lane]; a.gyro[first * 3 + lane] = GO[lane]; }
+}
 #undef A1_PL_MV
 #undef A1_PL_MTV
 
@@ -3424,6 +3582,85 @@ a1mpc_status a1mpc_plant_step_batch(a1mpc_handle h, const a1mpc_plant_config* cf
     sg.back(state_out, d_out, W); sg.back(R_world_out, d_R, 9); sg.back(foot_abs_out, d_foot, 12);
     A1_STAGED(sg);
     A1_STAGE_LAUNCH(launch_plant_step(h, *cfg, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_out, d_R, d_foot, s));
+    return sg.finish();
+}
+// ---- sensor synthesis behind the C ABI: a1mpc_sensor_synthesis_kernel, no handle state
+// what the two entries refuse, or null (all before the first HIP call; n > max_batch is A1_STAGE_DEVICE's)
+static const char* invalid_sensor_synthesis(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                            const double* grf_body, const uint8_t* contacts, const double* rho_fix, const double* rho_opt, const double* quat_out,
+                                            const double* imu_acc_raw_out, const double* imu_gyro_raw_out, const double* joint_pos_out, const double* joint_vel_out,
+                                            const double* foot_force_out, const uint8_t* reach_out) {
+    if (!h) return "null handle";
+    if (state_stride != 12 && state_stride != 13 && state_stride != 22) return "state_stride must be 12, 13 or 22";
+    if (n < 0) return "negative n";
+    if (!state) return "null state";
+    if (!R_world) return "null R_world";
+    if (!foot_abs) return "null foot_abs";
+    if (!grf_body) return "null grf_body";
+    if (!contacts) return "null contacts";
+    if (!rho_fix) return "null rho_fix";
+    if (!rho_opt) return "null rho_opt";
+    if (!quat_out) return "null quat_out";
+    if (!imu_acc_raw_out) return "null imu_acc_raw_out";
+    if (!imu_gyro_raw_out) return "null imu_gyro_raw_out";
+    if (!joint_pos_out) return "null joint_pos_out";
+    if (!joint_vel_out) return "null joint_vel_out";
+    if (!foot_force_out) return "null foot_force_out";
+    if (!reach_out) return "null reach_out";
+    for (int k = 0; k < 20; ++k) if (!std::isfinite(rho_fix[k])) return "rho_fix holds a value that is not finite";
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(rho_opt[k])) return "rho_opt holds a value that is not finite";
+    for (int l = 0; l < 4; ++l) {
+        const double lt = rho_fix[5 * l + 3], al = rho_fix[5 * l + 4] - rho_opt[3 * l + 2], r0 = rho_opt[3 * l];
+        if (!(lt > 0.0)) return "rho_fix: the upper leg length must be positive";
+        if (al * al + r0 * r0 == 0.0) return "rho_fix / rho_opt: the lower leg has no length";
+    }
+    return nullptr;
+}
+// the launch alone: device pointers (the geometry: host), validated by the caller, which also orders and marks the stream.  One wavefront per workgroup, 16 robots each
+static void launch_sensor_synthesis(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                    const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* rho_fix, const double* rho_opt, double* quat_out,
+                                    double* imu_acc_raw_out, double* imu_gyro_raw_out, double* joint_pos_out, double* joint_vel_out, double* foot_force_out,
+                                    uint8_t* reach_out, double* foot_pos_rel_out, double* foot_vel_rel_out, hipStream_t s) {
+    SynthArgs a;
+    a.n = n; a.stride = state_stride; a.mass = h->cfg.mass;
+    std::memcpy(a.rho_fix, rho_fix, sizeof a.rho_fix); std::memcpy(a.rho_opt, rho_opt, sizeof a.rho_opt);
+    a.state = state; a.R = R_world; a.foot = foot_abs; a.grf = grf_body; a.ext = ext_wrench; a.contacts = contacts;
+    a.quat = quat_out; a.acc = imu_acc_raw_out; a.gyro = imu_gyro_raw_out; a.jpos = joint_pos_out; a.jvel = joint_vel_out; a.fforce = foot_force_out;
+    a.prel = foot_pos_rel_out; a.vrel = foot_vel_rel_out; a.reach = reach_out;
+    hipLaunchKernelGGL(a1mpc_sensor_synthesis_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, a);
+}
+a1mpc_status a1mpc_sensor_synthesis_batch_device(a1mpc_handle h, int32_t n, const double* d_state, int32_t state_stride, const double* d_R_world, const double* d_foot_abs,
+                                                 const double* d_grf_body, const uint8_t* d_contacts, const double* d_ext_wrench, const double* rho_fix,
+                                                 const double* rho_opt, double* d_quat_out, double* d_imu_acc_raw_out, double* d_imu_gyro_raw_out, double* d_joint_pos_out,
+                                                 double* d_joint_vel_out, double* d_foot_force_out, uint8_t* d_reach_out, double* d_foot_pos_rel_out,
+                                                 double* d_foot_vel_rel_out, void* hip_stream) {
+    if (const char* bad = invalid_sensor_synthesis(h, n, d_state, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, rho_fix, rho_opt, d_quat_out, d_imu_acc_raw_out,
+                                                   d_imu_gyro_raw_out, d_joint_pos_out, d_joint_vel_out, d_foot_force_out, d_reach_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_sensor_synthesis(h, n, d_state, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_ext_wrench, rho_fix, rho_opt, d_quat_out,
+                                            d_imu_acc_raw_out, d_imu_gyro_raw_out, d_joint_pos_out, d_joint_vel_out, d_foot_force_out, d_reach_out, d_foot_pos_rel_out,
+                                            d_foot_vel_rel_out, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_sensor_synthesis_batch(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                          const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* rho_fix, const double* rho_opt,
+                                          double* quat_out, double* imu_acc_raw_out, double* imu_gyro_raw_out, double* joint_pos_out, double* joint_vel_out,
+                                          double* foot_force_out, uint8_t* reach_out, double* foot_pos_rel_out, double* foot_vel_rel_out) {
+    if (const char* bad = invalid_sensor_synthesis(h, n, state, state_stride, R_world, foot_abs, grf_body, contacts, rho_fix, rho_opt, quat_out, imu_acc_raw_out,
+                                                   imu_gyro_raw_out, joint_pos_out, joint_vel_out, foot_force_out, reach_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const double *d_state = sg.in(state, static_cast<size_t>(state_stride)), *d_R = sg.in(R_world, 9), *d_foot = sg.in(foot_abs, 12), *d_grf = sg.in(grf_body, 12);
+    const double* d_ext = ext_wrench ? sg.in(ext_wrench, 6) : nullptr;
+    const uint8_t* d_ct = sg.in(contacts, 4);
+    double *d_quat = sg.out(quat_out, 4), *d_acc = sg.out(imu_acc_raw_out, 3), *d_gyro = sg.out(imu_gyro_raw_out, 3), *d_jp = sg.out(joint_pos_out, 12);
+    double *d_jv = sg.out(joint_vel_out, 12), *d_ff = sg.out(foot_force_out, 4), *d_pr = sg.out(foot_pos_rel_out, 12), *d_vr = sg.out(foot_vel_rel_out, 12);
+    uint8_t* d_reach = sg.out(reach_out, 4);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_sensor_synthesis(h, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, rho_fix, rho_opt, d_quat, d_acc, d_gyro, d_jp, d_jv, d_ff, d_reach,
+                                            d_pr, d_vr, s));
     return sg.finish();
 }
 #undef A1_STAGE_BEGIN

@@ -89,7 +89,7 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
+EXPORTS = ["a1mpc_sensor_synthesis_batch", "a1mpc_sensor_synthesis_batch_device", "a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
            "a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
            "a1mpc_command_batch", "a1mpc_command_batch_device", "a1mpc_control_tick_sensors_device", "a1mpc_balance_wrench_kp_batch", "a1mpc_balance_wrench_kp_batch_device",
            "a1mpc_default_balance_gains", "a1mpc_balance_wrench_batch", "a1mpc_balance_wrench_batch_device", "a1mpc_balance_solve_batch_device", "a1mpc_contacts_batch",
@@ -221,6 +221,9 @@ def load_library(path=None):
         lib.a1mpc_default_plant_config.argtypes = [C.POINTER(PlantConfig)]; lib.a1mpc_default_plant_config.restype = None
         lib.a1mpc_plant_step_batch.argtypes = [vp, C.POINTER(PlantConfig), i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, dp]; lib.a1mpc_plant_step_batch.restype = C.c_int
         lib.a1mpc_plant_step_batch_device.argtypes = [vp, C.POINTER(PlantConfig), i32, vpp, i32] + [vpp] * 8 + [vpp]; lib.a1mpc_plant_step_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_sensor_synthesis_batch"):   # (sensor synthesis from the plant; an older build bound by hand for an A/B lacks it)
+        lib.a1mpc_sensor_synthesis_batch.argtypes = [vp, i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp] + [dp] * 6 + [u8p, dp, dp]; lib.a1mpc_sensor_synthesis_batch.restype = C.c_int
+        lib.a1mpc_sensor_synthesis_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 5 + [dp, dp] + [vpp] * 9 + [vpp]; lib.a1mpc_sensor_synthesis_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -541,6 +544,39 @@ class Engine:
                                                     _dev(d_ext_wrench), out(d_state_out, d_state), out(d_R_out, d_R), out(d_foot_out, d_foot),
                                                     C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_plant_step_batch_device")
+
+    # ---- what the robot's sensors read on that plant: the inverse of the tick's front stages, so that sensors -> tick -> plant -> sensors closes on the device ----
+    SYNTHESIS_OUTPUTS = ("quat", "imu_acc_raw", "imu_gyro_raw", "joint_pos", "joint_vel", "foot_force", "reach", "foot_pos_rel", "foot_vel_rel")
+
+    def sensor_synthesis(self, state, R, foot, grf, contacts, ext_wrench=None, rho_fix=None, rho_opt=None, want_foot_rel=True):
+        """dict(quat (n, 4) as w, x, y, z; imu_acc_raw, imu_gyro_raw (n, 3); joint_pos, joint_vel (n, 12); foot_force (n, 4); reach (n, 4) uint8; foot_pos_rel, foot_vel_rel
+        (n, 12), or None without want_foot_rel): a1mpc_sensor_synthesis_batch.  The inputs of plant_step (state (n, 12 | 13 | 22), of which omega and v are read) and the
+        leg geometry of leg_state"""
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6))
+        fix = _f64(self.A1_RHO_FIX if rho_fix is None else rho_fix, (4, 5)); opt = _f64(np.zeros((4, 3)) if rho_opt is None else rho_opt, (4, 3))
+        out = dict(quat=np.zeros((n, 4)), imu_acc_raw=np.zeros((n, 3)), imu_gyro_raw=np.zeros((n, 3)), joint_pos=np.zeros((n, 12)), joint_vel=np.zeros((n, 12)),
+                   foot_force=np.zeros((n, 4)), reach=np.zeros((n, 4), np.uint8), foot_pos_rel=np.zeros((n, 12)) if want_foot_rel else None,
+                   foot_vel_rel=np.zeros((n, 12)) if want_foot_rel else None)
+        rc = self.lib.a1mpc_sensor_synthesis_batch(self._h, n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(fix), _dp(opt), _dp(out["quat"]),
+                                                   _dp(out["imu_acc_raw"]), _dp(out["imu_gyro_raw"]), _dp(out["joint_pos"]), _dp(out["joint_vel"]), _dp(out["foot_force"]),
+                                                   _u8p(out["reach"]), _dp(out["foot_pos_rel"]), _dp(out["foot_vel_rel"]))
+        _check(self.lib, rc, "a1mpc_sensor_synthesis_batch")
+        return out
+
+    def sensor_synthesis_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_joint_pos, d_joint_vel, d_foot_force,
+                                d_reach, d_foot_pos_rel=None, d_foot_vel_rel=None, d_ext_wrench=None, rho_fix=None, rho_opt=None, stream=None):
+        """device pointers (torch tensors), asynchronous on `stream`: on the stream of the preceding plant_step_device it reads that step's outputs; rho_fix / rho_opt are
+        host arrays"""
+        fix = _f64(self.A1_RHO_FIX if rho_fix is None else rho_fix, (4, 5)); opt = _f64(np.zeros((4, 3)) if rho_opt is None else rho_opt, (4, 3))
+        rc = self.lib.a1mpc_sensor_synthesis_batch_device(self._h, int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf), _dev(d_contacts),
+                                                          _dev(d_ext_wrench), _dp(fix), _dp(opt), _dev(d_quat), _dev(d_imu_acc_raw), _dev(d_imu_gyro_raw), _dev(d_joint_pos),
+                                                          _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach), _dev(d_foot_pos_rel), _dev(d_foot_vel_rel),
+                                                          C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_sensor_synthesis_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

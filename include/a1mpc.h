@@ -757,6 +757,55 @@ a1mpc_status a1mpc_plant_step_batch_device(a1mpc_handle h, const a1mpc_plant_con
                                            const double* d_ext_wrench, double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, void* hip_stream);
 
 /*
+ * Sensor synthesis: what a robot's sensors read on the body a1mpc_plant_step_batch advances -- the inverse of the front stages of a1mpc_control_tick_sensors_device
+ * (quaternion -> R, joint angles -> feet, the EKF's accelerometer and foot-velocity relations), n robots.  With it  a1mpc_sensor_synthesis_batch_device ->
+ * a1mpc_control_tick_sensors_device -> a1mpc_plant_step_batch_device  runs on one stream with no host copy, and the estimator, the leg kinematics, the contact logic and
+ * the sensor front end are inside the loop.
+ * in: the layouts of a1mpc_plant_step_batch.  state n x state_stride (12, 13 or 22), of which only [6:9] omega and [9:12] v are read, both world frame; R_world n x 9
+ * row-major; foot_abs n x 12, r_l the lever of leg l; grf_body n x 12 and contacts n x 4: the forces that were applied; ext_wrench NULL or n x 6 (its force half is
+ * read); rho_fix (20) and rho_opt (12): HOST arrays in both entries, the leg geometry of a1mpc_leg_state_batch.  The mass is the handle's cfg.mass.
+ * Per robot, R row-major, every three-term sum left to right:
+ *   gyro        imu_gyro_raw = R^T omega
+ *   accelerometer  the specific force in the body frame:  imu_acc_raw = ((f_0 + f_1) + (f_2 + f_3)) / m,  then + (R^T f_ext) / m when a wrench is given; a swing leg
+ *               contributes exactly +0, selected and not multiplied, as in the plant.  This is R^T (a - g e_z) of the plant's step 3: no differencing and no gravity
+ *               constant (the EKF adds its own (0, 0, -9.81), A1BasicEKF.cpp:76)
+ *   foot force  foot_force_l = the world z component of R f_l,  (R20 f0 + R21 f1) + R22 f2,  for a stance leg; +0 for a swing leg
+ *   quaternion  (w, x, y, z) by Eigen's matrix-to-quaternion algorithm.  tr = (R00 + R11) + R22 > 0:  t = sqrt(tr + 1), w = t / 2, t = 0.5 / t, x = (R21 - R12) t,
+ *               y = (R02 - R20) t, z = (R10 - R01) t.  Otherwise i = the largest diagonal (0; 1 if R11 > R00; 2 if R22 > Rii), j = (i + 1) % 3, k = (j + 1) % 3:
+ *               t = sqrt(((Rii - Rjj) - Rkk) + 1), q_i = t / 2, t = 0.5 / t, w = (Rkj - Rjk) t, q_j = (Rji + Rij) t, q_k = (Rki + Rik) t
+ *   foot position  foot_pos_rel_l = p = R^T r_l
+ *   joint angles   the closed-form inverse of the leg model of a1mpc_leg_state_batch, with its ox = f[0], oy = f[1], L = f[2] + o[1], lt = f[3], al = f[4] - o[2],
+ *               r0 = o[0] (f = rho_fix + 5 l, o = rho_opt + 3 l):
+ *                 dx = p0 - ox,  dy = p1 - oy,  Zp = -sqrt(max((dy dy + p2 p2) - L L, 0)),  q0 = atan2(p2, dy) - atan2(Zp, L)
+ *                 ell = sqrt(al al + r0 r0),  phi = atan2(r0, al),  c = (((dx dx + Zp Zp) - lt lt) - ell ell) / ((2 lt) ell)
+ *                 k = -acos(clamp(c, -1, 1))   (the knee bends back, as the A1's does)
+ *                 q1 = atan2(-dx, -Zp) - atan2(ell sin k, lt + ell cos k),  q2 = k + phi
+ *   foot velocity  stance leg: foot_vel_rel_l = -(R^T (v + omega x r_l)), the foot at rest in the world (the relation A1BasicEKF.cpp:122 inverts); swing leg: exactly
+ *               +0, the foot fixed in the body (the plant's step 6)
+ *   joint rates    joint_vel_l = J(q)^-1 foot_vel_rel_l, J the leg model's Jacobian evaluated at the synthesised angles, the inverse by cofactors like the plant's I_b^-1
+ *   reach flags    reach_l bit 0: dy dy + p2 p2 < L L was clamped; bit 1: c was clamped.  Any bit set: this leg's joint_vel is exactly +0
+ * Arithmetic: contraction off, no fused multiply-add; IEEE +, -, *, / and sqrt, the device library's atan2, acos, sin and cos.  Each robot's outputs are a pure function
+ * of that robot's inputs alone: the same bits at every batch size, position in the batch and entry.
+ * What it is not: no sensor noise or bias, no ground or contact model (foot_force is the applied force, not a measured one); a swing foot is fixed in the body, as the
+ * plant keeps it, so the loop this closes is the standing robot.
+ * out: quat_out n x 4, imu_acc_raw_out and imu_gyro_raw_out n x 3, joint_pos_out and joint_vel_out n x 12, foot_force_out n x 4 doubles and reach_out n x 4 bytes, all
+ * required; foot_pos_rel_out and foot_vel_rel_out n x 12, optional (NULL = not wanted).  No output may alias an input.  Non-finite inputs of one robot stay with that robot.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the argument) before any launch: a null handle or required pointer, a state_stride other than
+ * 12 / 13 / 22, n < 0, a geometry value that is not finite, lt <= 0, al al + r0 r0 == 0; n > max_batch is A1MPC_ERR_BATCH_TOO_LARGE.  n == 0 is A1MPC_OK and launches
+ * nothing.  The handle gets no state.  Host pointers (staged like the other caller-side entries); the _device entry takes device pointers and is asynchronous on
+ * hip_stream (NULL = the handle's), ordered like every other _device entry.
+ */
+a1mpc_status a1mpc_sensor_synthesis_batch(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                          const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* rho_fix, const double* rho_opt,
+                                          double* quat_out, double* imu_acc_raw_out, double* imu_gyro_raw_out, double* joint_pos_out, double* joint_vel_out,
+                                          double* foot_force_out, uint8_t* reach_out, double* foot_pos_rel_out, double* foot_vel_rel_out);
+a1mpc_status a1mpc_sensor_synthesis_batch_device(a1mpc_handle h, int32_t n, const double* d_state, int32_t state_stride, const double* d_R_world,
+                                                 const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts, const double* d_ext_wrench,
+                                                 const double* rho_fix, const double* rho_opt, double* d_quat_out, double* d_imu_acc_raw_out,
+                                                 double* d_imu_gyro_raw_out, double* d_joint_pos_out, double* d_joint_vel_out, double* d_foot_force_out,
+                                                 uint8_t* d_reach_out, double* d_foot_pos_rel_out, double* d_foot_vel_rel_out, void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
