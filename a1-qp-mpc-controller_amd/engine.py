@@ -70,6 +70,10 @@ class PlantConfig(C.Structure):  # a1mpc_plant_config: one call of the single-ri
     _fields_ = [("dt", C.c_double), ("substeps", C.c_int32), ("gravity_z", C.c_double)]
 
 
+class WalkConfig(C.Structure):  # a1mpc_walk_config: the plant's configuration, how far a swing foot moves towards its target per call, the flat ground
+    _fields_ = [("plant", PlantConfig), ("swing_track", C.c_double), ("flat_ground", C.c_int32), ("ground_z", C.c_double)]
+
+
 TICK_SENSOR_POINTERS = ("quat", "imu_acc_raw", "imu_gyro_raw", "cmd", "mode_toggle", "body_height", "ctrl_state", "root_pos_d", "kp_linear_xy", "mpc_init_counter")
 COMMAND_STATE_FIELDS = ("body_height", "ctrl_state", "root_euler_d", "root_pos_d", "kp_linear_xy", "mpc_init_counter")   # carried by the caller, in the C ABI's order
 
@@ -89,7 +93,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_sensor_synthesis_batch", "a1mpc_sensor_synthesis_batch_device", "a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
+EXPORTS = ["a1mpc_default_walk_config", "a1mpc_walk_step_batch", "a1mpc_walk_step_batch_device", "a1mpc_walk_sensors_batch", "a1mpc_walk_sensors_batch_device",
+           "a1mpc_sensor_synthesis_batch", "a1mpc_sensor_synthesis_batch_device", "a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
            "a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
            "a1mpc_command_batch", "a1mpc_command_batch_device", "a1mpc_control_tick_sensors_device", "a1mpc_balance_wrench_kp_batch", "a1mpc_balance_wrench_kp_batch_device",
            "a1mpc_default_balance_gains", "a1mpc_balance_wrench_batch", "a1mpc_balance_wrench_batch_device", "a1mpc_balance_solve_batch_device", "a1mpc_contacts_batch",
@@ -224,6 +229,12 @@ def load_library(path=None):
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_sensor_synthesis_batch"):   # (sensor synthesis from the plant; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_sensor_synthesis_batch.argtypes = [vp, i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp] + [dp] * 6 + [u8p, dp, dp]; lib.a1mpc_sensor_synthesis_batch.restype = C.c_int
         lib.a1mpc_sensor_synthesis_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 5 + [dp, dp] + [vpp] * 9 + [vpp]; lib.a1mpc_sensor_synthesis_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_walk_step_batch"):   # (the walking plant and its sensors; an older build bound by hand for an A/B lacks them)
+        lib.a1mpc_default_walk_config.argtypes = [C.POINTER(WalkConfig)]; lib.a1mpc_default_walk_config.restype = None
+        lib.a1mpc_walk_step_batch.argtypes = [vp, C.POINTER(WalkConfig), i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, dp, dp, dp, dp]; lib.a1mpc_walk_step_batch.restype = C.c_int
+        lib.a1mpc_walk_step_batch_device.argtypes = [vp, C.POINTER(WalkConfig), i32, vpp, i32] + [vpp] * 11 + [vpp]; lib.a1mpc_walk_step_batch_device.restype = C.c_int
+        lib.a1mpc_walk_sensors_batch.argtypes = [vp, i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, dp] + [dp] * 6 + [u8p, dp, dp]; lib.a1mpc_walk_sensors_batch.restype = C.c_int
+        lib.a1mpc_walk_sensors_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 6 + [dp, dp] + [vpp] * 9 + [vpp]; lib.a1mpc_walk_sensors_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -577,6 +588,72 @@ class Engine:
                                                           _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach), _dev(d_foot_pos_rel), _dev(d_foot_vel_rel),
                                                           C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_sensor_synthesis_batch_device")
+
+    # ---- the walking plant: swing feet that move to the tick's swing target, a flat ground, and the sensors that know the swing feet move ----
+    def walk_config(self, **fields):
+        """a1mpc_default_walk_config (the default plant config, swing_track 1, flat_ground 0, ground_z 0) with `fields` overridden: dt, substeps, gravity_z (the plant's),
+        swing_track, flat_ground, ground_z"""
+        wc = WalkConfig(); self.lib.a1mpc_default_walk_config(C.byref(wc))
+        for k, v in fields.items():
+            tgt = wc.plant if hasattr(wc.plant, k) else wc
+            if not hasattr(tgt, k):
+                raise KeyError(k)
+            setattr(tgt, k, int(v) if k in ("substeps", "flat_ground") else float(v))
+        return wc
+
+    def walk_step(self, state, R, foot, grf, contacts, R_z=None, foot_target=None, ext_wrench=None, walk=None):
+        """dict(state, R, foot as plant_step; foot_vel_body (n, 12): the commanded body-frame velocity of the swing feet): a1mpc_walk_step_batch.  The inputs of plant_step,
+        R_z (n, 9) the tick's root_rot_mat_z and foot_target (n, 12) its foot_pos_target_last_time (both may be None with swing_track == 0)"""
+        wc = self.walk_config() if walk is None else walk
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6))
+        Rz = None if R_z is None else _f64(R_z, (n, 9)); tg = None if foot_target is None else _f64(foot_target, (n, 12))
+        state_out = state.copy(); R_out = np.zeros((n, 9)); foot_out = np.zeros((n, 12)); vel_out = np.zeros((n, 12))
+        rc = self.lib.a1mpc_walk_step_batch(self._h, C.byref(wc), n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(Rz), _dp(tg), _dp(state_out),
+                                            _dp(R_out), _dp(foot_out), _dp(vel_out))
+        _check(self.lib, rc, "a1mpc_walk_step_batch")
+        return dict(state=state_out, R=R_out, foot=foot_out, foot_vel_body=vel_out)
+
+    def walk_step_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_R_z, d_foot_target, d_foot_vel_body, d_ext_wrench=None, d_state_out=None,
+                         d_R_out=None, d_foot_out=None, walk=None, stream=None):
+        """device pointers (torch tensors), asynchronous on `stream`: on the stream of the preceding control_tick_*_device it reads that tick's grf, contacts, R_z and
+        foot_pos_target_last_time.  An output left None is its input: the step runs in place; d_foot_vel_body is written"""
+        wc = self.walk_config() if walk is None else walk
+        out = lambda o, i: _dev(i if o is None else o)
+        rc = self.lib.a1mpc_walk_step_batch_device(self._h, C.byref(wc), int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf), _dev(d_contacts),
+                                                   _dev(d_ext_wrench), _dev(d_R_z), _dev(d_foot_target), out(d_state_out, d_state), out(d_R_out, d_R), out(d_foot_out, d_foot),
+                                                   _dev(d_foot_vel_body), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_walk_step_batch_device")
+
+    def walk_sensors(self, state, R, foot, grf, contacts, foot_vel_body=None, ext_wrench=None, rho_fix=None, rho_opt=None, want_foot_rel=True):
+        """the dict of sensor_synthesis: a1mpc_walk_sensors_batch.  foot_vel_body (n, 12) or None: the walk step's commanded swing-foot velocity"""
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6)); vel = None if foot_vel_body is None else _f64(foot_vel_body, (n, 12))
+        fix = _f64(self.A1_RHO_FIX if rho_fix is None else rho_fix, (4, 5)); opt = _f64(np.zeros((4, 3)) if rho_opt is None else rho_opt, (4, 3))
+        out = dict(quat=np.zeros((n, 4)), imu_acc_raw=np.zeros((n, 3)), imu_gyro_raw=np.zeros((n, 3)), joint_pos=np.zeros((n, 12)), joint_vel=np.zeros((n, 12)),
+                   foot_force=np.zeros((n, 4)), reach=np.zeros((n, 4), np.uint8), foot_pos_rel=np.zeros((n, 12)) if want_foot_rel else None,
+                   foot_vel_rel=np.zeros((n, 12)) if want_foot_rel else None)
+        rc = self.lib.a1mpc_walk_sensors_batch(self._h, n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(vel), _dp(fix), _dp(opt), _dp(out["quat"]),
+                                               _dp(out["imu_acc_raw"]), _dp(out["imu_gyro_raw"]), _dp(out["joint_pos"]), _dp(out["joint_vel"]), _dp(out["foot_force"]),
+                                               _u8p(out["reach"]), _dp(out["foot_pos_rel"]), _dp(out["foot_vel_rel"]))
+        _check(self.lib, rc, "a1mpc_walk_sensors_batch")
+        return out
+
+    def walk_sensors_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_joint_pos, d_joint_vel, d_foot_force,
+                            d_reach, d_foot_pos_rel=None, d_foot_vel_rel=None, d_ext_wrench=None, d_foot_vel_body=None, rho_fix=None, rho_opt=None, stream=None):
+        """sensor_synthesis_device with d_foot_vel_body: on the stream of the preceding walk_step_device it reads that step's outputs"""
+        fix = _f64(self.A1_RHO_FIX if rho_fix is None else rho_fix, (4, 5)); opt = _f64(np.zeros((4, 3)) if rho_opt is None else rho_opt, (4, 3))
+        rc = self.lib.a1mpc_walk_sensors_batch_device(self._h, int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf), _dev(d_contacts),
+                                                      _dev(d_ext_wrench), _dev(d_foot_vel_body), _dp(fix), _dp(opt), _dev(d_quat), _dev(d_imu_acc_raw), _dev(d_imu_gyro_raw),
+                                                      _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach), _dev(d_foot_pos_rel), _dev(d_foot_vel_rel),
+                                                      C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_walk_sensors_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

@@ -806,6 +806,58 @@ a1mpc_status a1mpc_sensor_synthesis_batch_device(a1mpc_handle h, int32_t n, cons
                                                  uint8_t* d_reach_out, double* d_foot_pos_rel_out, double* d_foot_vel_rel_out, void* hip_stream);
 
 /*
+ * The walking plant: a1mpc_plant_step_batch with swing feet that MOVE in the body frame and a flat rigid ground, and the sensors that know the swing feet move.  With
+ * them  a1mpc_walk_sensors_batch_device -> a1mpc_control_tick_sensors_device -> a1mpc_walk_step_batch_device  runs on one stream with no host copy while the gait layer
+ * (update_plan, the Bezier swing legs, the contact logic) walks the body: in movement_mode 1 the loop this closes is the trotting robot.  The plant step and the sensor
+ * synthesis above are unchanged and stay the standing robot's.
+ *
+ * a1mpc_walk_step_batch.  Layouts, strides 12 / 13 / 22, the in-place rule of state / R_world / foot_abs, mass and inertia (the handle's) are those of
+ * a1mpc_plant_step_batch; cfg->plant is its configuration.  Step 0 (the polish of R) and steps 1 - 5 of every sub-step are its steps, in its operation order.  New:
+ *   in   R_z          n x 9 row-major: the tick's root_rot_mat_z (a1mpc_tick_buffers.R_z)
+ *        foot_target  n x 12: the tick's foot_pos_target_last_time, y_l = the Bezier point the swing-leg stage asked leg l to be at on this tick, in the frame of
+ *                     foot_pos_cur = R_z^T foot_pos_abs.  Both are device-resident outputs / carried state of a1mpc_control_tick_device
+ *   before the sub-steps, with R the polished attitude, for every leg:  p0 = R^T r,  p_t = R^T (R_z y),  d = (swing_track (p_t - p0)) / substeps,
+ *        vel = (swing_track (p_t - p0)) / dt.  swing_track == 0: d and vel are exactly +0, selected and not multiplied; R_z and foot_target are not read and may be NULL
+ *   step 6 of a sub-step:  a stance foot keeps r' = r - dp;  a swing foot does p = R^T r, p' = p + d, r' = R' p'  (swing_track == 0: p' = p, the sum is skipped, so the
+ *        step is a1mpc_plant_step_batch's bit for bit)
+ *   after the last sub-step, when flat_ground != 0, with gz = ground_z - pos_z':  a stance foot gets r'_z = gz (ON the plane z = ground_z of the world);  a swing foot
+ *        gets r'_z = (r'_z < gz) ? gz : r'_z (not below it; a NaN stays a NaN)
+ *   out  foot_vel_body_out n x 12, required: a swing leg writes vel, the COMMANDED body-frame velocity of its foot over this call; a stance leg writes +0.  It is the
+ *        commanded velocity: on a tick where the ground stops the foot it overstates the z motion.  a1mpc_walk_sensors_batch reads it
+ * A stance leg's foot_target reaches no output (selected away, like a swing leg's force): a NaN there changes no bit.  swing_track in (0, 1) moves the foot that
+ * fraction of the way per call.  The default configuration is a1mpc_default_plant_config, swing_track 1, flat_ground 0, ground_z 0.
+ * What it is not: a kinematic swing over a flat rigid plane.  Legs are massless; there is no impact and no slip; no friction cone is applied to the given forces;
+ * nothing stops the BODY itself at the plane; and the foot-force sensor of a1mpc_walk_sensors_batch is still the applied force, not a measured touchdown, so the
+ * reference's early-contact branch never fires.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch: everything a1mpc_plant_step_batch refuses (on cfg->plant), a null
+ * foot_vel_body_out, a swing_track outside [0, 1] or not finite, flat_ground set with a ground_z that is not finite, swing_track > 0 with a NULL R_z or foot_target.
+ * n == 0 is A1MPC_OK and launches nothing.  The handle gets no state.  Host pointers, or (_device) device pointers, asynchronous on hip_stream.
+ *
+ * a1mpc_walk_sensors_batch is a1mpc_sensor_synthesis_batch with one more input, foot_vel_body (n x 12, optional) after ext_wrench: on a SWING leg foot_vel_rel_l is
+ * foot_vel_body_l (selected) instead of +0, and joint_vel_l = J(q)^-1 of it by the same cofactor inverse; the reach-flag rule (any bit set: joint_vel_l = +0) is
+ * unchanged; a stance leg's foot_vel_body reaches no output.  Everything else is the synthesis's arithmetic, layouts and refusals; with foot_vel_body NULL or all +0
+ * every output is a1mpc_sensor_synthesis_batch's bit for bit.
+ */
+typedef struct a1mpc_walk_config { a1mpc_plant_config plant; double swing_track; int32_t flat_ground; double ground_z; } a1mpc_walk_config;
+void a1mpc_default_walk_config(a1mpc_walk_config* cfg);   /* a1mpc_default_plant_config, 1.0, 0, 0.0 */
+a1mpc_status a1mpc_walk_step_batch(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                   const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                   const double* foot_target, double* state_out, double* R_world_out, double* foot_abs_out, double* foot_vel_body_out);
+a1mpc_status a1mpc_walk_step_batch_device(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                          const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                          const double* d_ext_wrench, const double* d_R_z, const double* d_foot_target, double* d_state_out, double* d_R_world_out,
+                                          double* d_foot_abs_out, double* d_foot_vel_body_out, void* hip_stream);
+a1mpc_status a1mpc_walk_sensors_batch(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                      const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* foot_vel_body, const double* rho_fix,
+                                      const double* rho_opt, double* quat_out, double* imu_acc_raw_out, double* imu_gyro_raw_out, double* joint_pos_out,
+                                      double* joint_vel_out, double* foot_force_out, uint8_t* reach_out, double* foot_pos_rel_out, double* foot_vel_rel_out);
+a1mpc_status a1mpc_walk_sensors_batch_device(a1mpc_handle h, int32_t n, const double* d_state, int32_t state_stride, const double* d_R_world, const double* d_foot_abs,
+                                             const double* d_grf_body, const uint8_t* d_contacts, const double* d_ext_wrench, const double* d_foot_vel_body,
+                                             const double* rho_fix, const double* rho_opt, double* d_quat_out, double* d_imu_acc_raw_out, double* d_imu_gyro_raw_out,
+                                             double* d_joint_pos_out, double* d_joint_vel_out, double* d_foot_force_out, uint8_t* d_reach_out,
+                                             double* d_foot_pos_rel_out, double* d_foot_vel_rel_out, void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
