@@ -1272,6 +1272,348 @@ __global__ __launch_bounds__(64) void a1mpc_walk_sensors_kernel(const WalkSensor
     if (lane < live * 4) a.quat[first * 4 + lane] = QO[lane];
     if (lane < live * 3) { a.acc[first * 3 + lane] = AO[lane]; a.gyro[first * 3 + lane] = GO[lane]; }
 }
+
+// ---- sloped ground and sensed touchdowns (a1mpc_ground_step_batch, a1mpc_touch_sensors_batch): the two walk kernels above with a ground plane PER ROBOT,
+// hz(X, Y) = (z0 + sx X) + sy Y in the world, and a touch byte per leg that says whether the ground holds the foot.  Third copies, not templates of the two above: those
+// keep their text, their code objects and their host emulation byte for byte.  The scheme is stated in include/a1mpc.h and restated elementwise in tests/ground_ref.py.
+//   lanes, memory, bits, dead lanes   those of a1mpc_walk_step_kernel.  A robot's plane (three words, shared by its four lanes) passes through wave-private LDS like
+//             R_z; the touch byte is a lane's own: stored (out of the step) and loaded (into the sensors) directly.  ground null: cfg's plane z = ground_z, or none.
+struct WalkGroundArgs {
+    WalkArgs w;
+    const double* ground;   // may be null: then w.flat_ground / w.ground_z decide
+    uint8_t* touch;
+};
+__global__ __launch_bounds__(64) void a1mpc_walk_step_ground_kernel(const WalkGroundArgs ga) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double glds[kPlState + kPlR + kPlExt + kPlR + 16 * 3];
+    double* const S = glds; double* const RL = glds + kPlState; double* const E = glds + kPlState + kPlR; double* const ZL = glds + kPlState + kPlR + kPlExt;
+    double* const GL = glds + kPlState + kPlR + kPlExt + kPlR;
+    const WalkArgs& wa = ga.w;
+    const PlantArgs& a = wa.p;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, stride = a.stride;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    const bool track = wa.track != 0.0, sloped = ga.ground != nullptr;
+    // every load, then the LDS writes, as in the walk step; the planes are 48 words at most: one load per lane
+    const int cs = live * stride, cr = live * 9, ce = a.ext ? live * 6 : 0, cz = track ? cr : 0, cg = sloped ? live * 3 : 0;
+    const double *gs = a.state + first * stride, *gr = a.R + first * 9, *ge = a.ext ? a.ext + first * 6 : a.R, *gzp = track ? wa.Rz + first * 9 : a.R;
+    const double* gg = sloped ? ga.ground + first * 3 : a.R;
+    double vs[6], vr[3], ve[2], vz[3];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; vs[m] = gs[e < cs ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vr[m] = gr[e < cr ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; ve[m] = ge[e < ce ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vz[m] = gzp[e < cz ? e : 0]; }
+    const double vg = gg[lane < cg ? lane : 0];
+    double r[3], f[3], y[3];
+    {
+        const double *fp = a.foot + b * 12 + 3 * l, *gp = a.grf + b * 12 + 3 * l, *tp = track ? wa.target + b * 12 + 3 * l : fp;
+        r[0] = fp[0]; r[1] = fp[1]; r[2] = fp[2]; f[0] = gp[0]; f[1] = gp[1]; f[2] = gp[2]; y[0] = tp[0]; y[1] = tp[1]; y[2] = tp[2];
+    }
+    const bool stance = a.contacts[b * 4 + l] != 0;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; if (e < cs) S[e] = vs[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cr) RL[e] = vr[m]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; if (e < ce) E[e] = ve[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cz) ZL[e] = vz[m]; }
+    if (lane < cg) GL[lane] = vg;
+    WaveStage::sync();
+    double pos[3], w[3], v[3], R[9], fe[3] = {0.0, 0.0, 0.0}, te[3] = {0.0, 0.0, 0.0};
+    {
+        const double* x = S + q * stride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pos[k] = x[3 + k]; w[k] = x[6 + k]; v[k] = x[9 + k]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = RL[q * 9 + k];
+    }
+    const bool with_ext = a.ext != nullptr;
+    if (with_ext) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { fe[k] = E[q * 6 + k]; te[k] = E[q * 6 + 3 + k]; }
+    }
+    // 0: the plant step's polish of R, I_b^-1 and L
+    {
+        double E[9], Rp[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) E[3 * i + j] = (R[i] * R[j] + R[3 + i] * R[3 + j]) + R[6 + i] * R[6 + j];
+        E[0] = E[0] - 1.0; E[4] = E[4] - 1.0; E[8] = E[8] - 1.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Rp[3 * i + j] = R[3 * i + j] - 0.5 * ((R[3 * i] * E[j] + R[3 * i + 1] * E[3 + j]) + R[3 * i + 2] * E[6 + j]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rp[k];
+    }
+    double Ii[9], L[3];
+    {
+        const double* I = a.inertia;
+        const double c00 = I[4] * I[8] - I[5] * I[7], c01 = I[5] * I[6] - I[3] * I[8], c02 = I[3] * I[7] - I[4] * I[6];
+        const double id = 1.0 / ((I[0] * c00 + I[1] * c01) + I[2] * c02);
+        Ii[0] = c00 * id; Ii[1] = (I[2] * I[7] - I[1] * I[8]) * id; Ii[2] = (I[1] * I[5] - I[2] * I[4]) * id;
+        Ii[3] = c01 * id; Ii[4] = (I[0] * I[8] - I[2] * I[6]) * id; Ii[5] = (I[2] * I[3] - I[0] * I[5]) * id;
+        Ii[6] = c02 * id; Ii[7] = (I[1] * I[6] - I[0] * I[7]) * id; Ii[8] = (I[0] * I[4] - I[1] * I[3]) * id;
+        double wb[3], Iw[3];
+        A1_PL_MTV(wb, R, w); A1_PL_MV(Iw, I, wb); A1_PL_MV(L, R, Iw);
+    }
+    // the swing foot's move over the call: the walk step's
+    double d[3] = {0.0, 0.0, 0.0}, vel[3] = {0.0, 0.0, 0.0};
+    if (track) {
+        double Rz[9], p0[3], tw[3], pt[3];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rz[k] = ZL[q * 9 + k];
+        A1_PL_MTV(p0, R, r); A1_PL_MV(tw, Rz, y); A1_PL_MTV(pt, R, tw);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double dl = wa.track * (pt[k] - p0[k]);
+            d[k] = dl / static_cast<double>(a.substeps); vel[k] = dl / a.dt;
+        }
+    }
+    const double h = a.dt / static_cast<double>(a.substeps), half = h / 2.0, m = a.mass, g = a.gravity;
+    for (int step = 0; step < a.substeps; ++step) {
+        // 1 .. 6: the walk step's
+        double fw[3], F[3], T[3];
+        A1_PL_MV(fw, R, f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fw[k] = stance ? fw[k] : 0.0;
+        const double tq[3] = {r[1] * fw[2] - r[2] * fw[1], r[2] * fw[0] - r[0] * fw[2], r[0] * fw[1] - r[1] * fw[0]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            F[k] = pl_legs(fw[k]); T[k] = pl_legs(tq[k]);
+            if (with_ext) { F[k] = F[k] + fe[k]; T[k] = T[k] + te[k]; }
+        }
+        double dp[3];
+        v[0] = v[0] + h * (F[0] / m); v[1] = v[1] + h * (F[1] / m); v[2] = v[2] + h * (F[2] / m + g);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { dp[k] = h * v[k]; pos[k] = pos[k] + dp[k]; }
+        double Rn[9];
+        {
+            const double a0 = half * w[0], a1 = half * w[1], a2 = half * w[2];
+            const double s = 2.0 / (1.0 + ((a0 * a0 + a1 * a1) + a2 * a2));
+            const double Cm[9] = {1.0 - s * (a1 * a1 + a2 * a2), s * (a0 * a1 - a2), s * (a0 * a2 + a1),
+                                  s * (a0 * a1 + a2), 1.0 - s * (a0 * a0 + a2 * a2), s * (a1 * a2 - a0),
+                                  s * (a0 * a2 - a1), s * (a1 * a2 + a0), 1.0 - s * (a0 * a0 + a1 * a1)};
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Cm[3 * i] * R[j] + Cm[3 * i + 1] * R[3 + j]) + Cm[3 * i + 2] * R[6 + j];
+        }
+        {
+            double Lb[3], wb[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) L[k] = L[k] + h * T[k];
+            A1_PL_MTV(Lb, Rn, L); A1_PL_MV(wb, Ii, Lb); A1_PL_MV(w, Rn, wb);
+        }
+        {
+            double rb[3], rs[3];
+            A1_PL_MTV(rb, R, r);
+            if (track) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) rb[k] = rb[k] + d[k];
+            }
+            A1_PL_MV(rs, Rn, rb);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) r[k] = stance ? r[k] - dp[k] : rs[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    }
+    // the ground, once per call, straight down: a stance foot ON its robot's plane under its own x and y, a swing foot not below it.  touch: stance, or the comparison
+    // that lifted the swing foot (a NaN compares false: the foot keeps its z and touch is 0).  No ground at all: a swing leg touches nothing
+    bool touch = stance;
+    if (sloped || wa.flat_ground) {
+        double top = wa.ground_z;
+        if (sloped) {   // (the plane's words wait in LDS until here: its image is not written again)
+            const double z0 = GL[q * 3], sx = GL[q * 3 + 1], sy = GL[q * 3 + 2];
+            const double X = pos[0] + r[0], Y = pos[1] + r[1];
+            top = (z0 + sx * X) + sy * Y;
+        }
+        const double gz = top - pos[2];
+        const bool lifted = r[2] < gz;
+        r[2] = stance ? gz : (lifted ? gz : r[2]);
+        touch = stance || lifted;
+    }
+    const double sp = -R[6], spc = sp > 1.0 ? 1.0 : (sp < -1.0 ? -1.0 : sp);   // (a NaN stays a NaN)
+    const double roll = atan2(R[7], R[8]), pitch = asin(spc), yaw = atan2(R[3], R[0]);
+    WaveStage::sync();   // (every lane has read its inputs)
+    if (alive) {
+        double* x = S + q * stride + 3 * l;
+        x[0] = pl_pick(l, roll, pos[0], w[0], v[0]); x[1] = pl_pick(l, pitch, pos[1], w[1], v[1]); x[2] = pl_pick(l, yaw, pos[2], w[2], v[2]);
+        if (l < 3) {
+            double* o = RL + q * 9 + 3 * l;
+            o[0] = pl_pick(l, R[0], R[3], R[6], 0.0); o[1] = pl_pick(l, R[1], R[4], R[7], 0.0); o[2] = pl_pick(l, R[2], R[5], R[8], 0.0);
+        }
+        double *fo = a.foot_out + b * 12 + 3 * l, *vo = wa.vel_out + b * 12 + 3 * l;
+        fo[0] = r[0]; fo[1] = r[1]; fo[2] = r[2];
+        vo[0] = stance ? 0.0 : vel[0]; vo[1] = stance ? 0.0 : vel[1]; vo[2] = stance ? 0.0 : vel[2];
+        ga.touch[b * 4 + l] = touch ? uint8_t{1} : uint8_t{0};
+    }
+    WaveStage::sync();
+    double *os = a.state_out + first * stride, *orr = a.R_out + first * 9;
+#pragma unroll
+    for (int mm = 0; mm < 6; ++mm) {
+        const int e = lane + 64 * mm;
+        const int col = stride == 12 ? e % 12 : (stride == 13 ? e % 13 : e % 22);
+        if (e < cs && col < 12) os[e] = S[e];
+    }
+#pragma unroll
+    for (int mm = 0; mm < 3; ++mm) { const int e = lane + 64 * mm; if (e < cr) orr[e] = RL[e]; }
+}
+
+// the sensors of the walking plant with a touch sensor: a1mpc_walk_sensors_kernel's arithmetic, except that a swing leg whose touch byte is set reports touch_force
+// (selected, not added; a stance leg's byte reaches no output).  touch null, or touch_force == +0: the walk sensors' bits
+struct WalkTouchArgs {
+    WalkSensorArgs w;
+    const uint8_t* touch;   // may be null
+    double touch_force;
+};
+__global__ __launch_bounds__(64) void a1mpc_walk_sensors_touch_kernel(const WalkTouchArgs ta) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double tlds[kPlState + kPlR + kPlExt];
+    double* const S = tlds; double* const RL = tlds + kPlState; double* const E = tlds + kPlState + kPlR;
+    const WalkSensorArgs& wa = ta.w;
+    const SynthArgs& a = wa.s;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, stride = a.stride;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    // every load, then the LDS writes, as in the plant step
+    const int cs = live * stride, cr = live * 9, ce = a.ext ? live * 6 : 0;
+    const double *gs = a.state + first * stride, *gr = a.R + first * 9, *ge = a.ext ? a.ext + first * 6 : a.R;
+    double vs[6], vr[3], ve[2];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; vs[m] = gs[e < cs ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vr[m] = gr[e < cr ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; ve[m] = ge[e < ce ? e : 0]; }
+    double r[3], f[3], fb[3];
+    {
+        const double *fp = a.foot + b * 12 + 3 * l, *gp = a.grf + b * 12 + 3 * l, *vp = wa.vel ? wa.vel + b * 12 + 3 * l : fp;
+        r[0] = fp[0]; r[1] = fp[1]; r[2] = fp[2]; f[0] = gp[0]; f[1] = gp[1]; f[2] = gp[2]; fb[0] = vp[0]; fb[1] = vp[1]; fb[2] = vp[2];
+    }
+    const bool stance = a.contacts[b * 4 + l] != 0, with_vel = wa.vel != nullptr;
+    const bool touched = (ta.touch ? ta.touch : a.contacts)[b * 4 + l] != 0 && ta.touch != nullptr;
+    const double *gf = a.rho_fix + 5 * l, *go = a.rho_opt + 3 * l;
+    const double ox = gf[0], oy = gf[1], L = gf[2] + go[1], lt = gf[3], al = gf[4] - go[2], r0 = go[0];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; if (e < cs) S[e] = vs[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cr) RL[e] = vr[m]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; if (e < ce) E[e] = ve[m]; }
+    WaveStage::sync();
+    double w[3], v[3], R[9], fe[3] = {0.0, 0.0, 0.0};
+    {
+        const double* x = S + q * stride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { w[k] = x[6 + k]; v[k] = x[9 + k]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = RL[q * 9 + k];
+    }
+    const bool with_ext = a.ext != nullptr;
+    if (with_ext) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fe[k] = E[q * 6 + k];
+    }
+    const double m = a.mass;
+    double gyro[3], acc[3];
+    A1_PL_MTV(gyro, R, w);
+    {
+        double feb[3];
+        A1_PL_MTV(feb, R, fe);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[k] = pl_legs(stance ? f[k] : 0.0) / m;
+            if (with_ext) acc[k] = acc[k] + feb[k] / m;
+        }
+    }
+    // the foot-force sensor: a stance leg's applied force along the world's z; a swing leg the ground holds reports the constant, any other swing leg +0
+    const double ff = stance ? (R[6] * f[0] + R[7] * f[1]) + R[8] * f[2] : (touched ? ta.touch_force : 0.0);
+    double qt[4];
+    {
+        const double tr = (R[0] + R[4]) + R[8];
+        const bool pos = tr > 0.0;
+        const int i = R[4] > R[0] ? (R[8] > R[4] ? 2 : 1) : (R[8] > R[0] ? 2 : 0);
+        const double dii = pl_pick(i, R[0], R[4], R[8], 0.0), djj = pl_pick(i, R[4], R[8], R[0], 0.0), dkk = pl_pick(i, R[8], R[0], R[4], 0.0);
+        const double kj = pl_pick(i, R[7], R[2], R[3], 0.0), jk = pl_pick(i, R[5], R[6], R[1], 0.0);
+        const double ji = pl_pick(i, R[3], R[7], R[2], 0.0), ij = pl_pick(i, R[1], R[5], R[6], 0.0);
+        const double ki = pl_pick(i, R[6], R[1], R[5], 0.0), ik = pl_pick(i, R[2], R[3], R[7], 0.0);
+        const double t = sqrt(pos ? tr + 1.0 : ((dii - djj) - dkk) + 1.0), hq = 0.5 * t, u = 0.5 / t;
+        const double qi = hq, qw4 = (kj - jk) * u, qj = (ji + ij) * u, qk = (ki + ik) * u;
+        qt[0] = pos ? hq : qw4;
+        qt[1] = pos ? (R[7] - R[5]) * u : pl_pick(i, qi, qk, qj, 0.0);
+        qt[2] = pos ? (R[2] - R[6]) * u : pl_pick(i, qj, qi, qk, 0.0);
+        qt[3] = pos ? (R[3] - R[1]) * u : pl_pick(i, qk, qj, qi, 0.0);
+    }
+    double p[3], jq[3];
+    A1_PL_MTV(p, R, r);
+    const double dx = p[0] - ox, dy = p[1] - oy;
+    const double yz = dy * dy + p[2] * p[2], LL = L * L;
+    const bool clamp0 = yz < LL;
+    const double Zi = -sqrt(clamp0 ? 0.0 : yz - LL);
+    jq[0] = atan2(p[2], dy) - atan2(Zi, L);
+    const double ell = sqrt(al * al + r0 * r0), phi = atan2(r0, al);
+    const double cq = (((dx * dx + Zi * Zi) - lt * lt) - ell * ell) / ((2.0 * lt) * ell);
+    const bool clamp1 = cq < -1.0 || cq > 1.0;
+    const double kn = -acos(cq > 1.0 ? 1.0 : (cq < -1.0 ? -1.0 : cq));   // (a NaN stays a NaN)
+    jq[1] = atan2(-dx, -Zi) - atan2(ell * sin(kn), lt + ell * cos(kn));
+    jq[2] = kn + phi;
+    const int flags = (clamp0 ? 1 : 0) | (clamp1 ? 2 : 0);
+    double fv[3];
+    {
+        const double u[3] = {v[0] + (w[1] * r[2] - w[2] * r[1]), v[1] + (w[2] * r[0] - w[0] * r[2]), v[2] + (w[0] * r[1] - w[1] * r[0])};
+        double ub[3];
+        A1_PL_MTV(ub, R, u);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fv[k] = stance ? -ub[k] : (with_vel ? fb[k] : 0.0);
+    }
+    double jd[3];
+    {
+        const double s0 = sin(jq[0]), c0 = cos(jq[0]), s1 = sin(jq[1]), c1 = cos(jq[1]), s12 = sin(jq[1] + jq[2]), c12 = cos(jq[1] + jq[2]);
+        const double Xq = r0 * c12 - al * s12, Zq = -(al * c12) - r0 * s12;
+        const double Xr = Xq - lt * s1, Zp = Zq - lt * c1;
+        const double py = oy + (L * c0 - Zp * s0), pz = L * s0 + Zp * c0;
+        const double I[9] = {0.0, Zp, Zq, -pz, s0 * Xr, s0 * Xq, py - oy, -(c0 * Xr), -(c0 * Xq)};
+        const double c00 = I[4] * I[8] - I[5] * I[7], c01 = I[5] * I[6] - I[3] * I[8], c02 = I[3] * I[7] - I[4] * I[6];
+        const double id = 1.0 / ((I[0] * c00 + I[1] * c01) + I[2] * c02);
+        const double Ji[9] = {c00 * id, (I[2] * I[7] - I[1] * I[8]) * id, (I[1] * I[5] - I[2] * I[4]) * id,
+                              c01 * id, (I[0] * I[8] - I[2] * I[6]) * id, (I[2] * I[3] - I[0] * I[5]) * id,
+                              c02 * id, (I[1] * I[6] - I[0] * I[7]) * id, (I[0] * I[4] - I[1] * I[3]) * id};
+        A1_PL_MV(jd, Ji, fv);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) jd[k] = flags ? 0.0 : jd[k];
+    }
+    WaveStage::sync();
+    double* const QO = S; double* const AO = S + 64; double* const GO = S + 112;
+    if (alive) {
+        double *o0 = a.jpos + b * 12 + 3 * l, *o1 = a.jvel + b * 12 + 3 * l;
+        o0[0] = jq[0]; o0[1] = jq[1]; o0[2] = jq[2]; o1[0] = jd[0]; o1[1] = jd[1]; o1[2] = jd[2];
+        if (a.prel) { double* o = a.prel + b * 12 + 3 * l; o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; }
+        if (a.vrel) { double* o = a.vrel + b * 12 + 3 * l; o[0] = fv[0]; o[1] = fv[1]; o[2] = fv[2]; }
+        a.fforce[b * 4 + l] = ff;
+        a.reach[b * 4 + l] = static_cast<uint8_t>(flags);
+        QO[q * 4 + l] = pl_pick(l, qt[0], qt[1], qt[2], qt[3]);
+        if (l < 3) { AO[q * 3 + l] = pl_pick(l, acc[0], acc[1], acc[2], 0.0); GO[q * 3 + l] = pl_pick(l, gyro[0], gyro[1], gyro[2], 0.0); }
+    }
+    WaveStage::sync();
+    if (lane < live * 4) a.quat[first * 4 + lane] = QO[lane];
+    if (lane < live * 3) { a.acc[first * 3 + lane] = AO[lane]; a.gyro[first * 3 + lane] = GO[lane]; }
+}
 #undef A1_PL_MV
 #undef A1_PL_MTV
 
@@ -4108,6 +4450,132 @@ a1mpc_status a1mpc_walk_sensors_batch(a1mpc_handle h, int32_t n, const double* s
     A1_STAGED(sg);
     A1_STAGE_LAUNCH(launch_walk_sensors(h, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_vel, rho_fix, rho_opt, d_quat, d_acc, d_gyro, d_jp, d_jv, d_ff, d_reach,
                                         d_pr, d_vr, s));
+    return sg.finish();
+}
+// ---- sloped ground and sensed touchdowns behind the C ABI: a1mpc_walk_step_ground_kernel and a1mpc_walk_sensors_touch_kernel, no handle state
+// what the two ground-step entries refuse, or null: the walk step's refusals (with `ground` given, cfg's own plane is not read and so not checked), then a null touch_out
+static const char* invalid_walk_step_ground(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                            const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* R_z, const double* foot_target,
+                                            const double* ground, const double* state_out, const double* R_world_out, const double* foot_abs_out,
+                                            const double* foot_vel_body_out, const uint8_t* touch_out) {
+    if (!h) return "null handle";
+    if (!cfg) return "null a1mpc_walk_config";
+    a1mpc_walk_config c = *cfg;
+    if (ground) { c.flat_ground = 0; c.ground_z = 0.0; }
+    if (const char* bad = invalid_walk_step(h, &c, n, state_in, state_stride, R_world, foot_abs, grf_body, contacts, R_z, foot_target, state_out, R_world_out, foot_abs_out,
+                                            foot_vel_body_out))
+        return bad;
+    if (!touch_out) return "null touch_out";
+    return nullptr;
+}
+static void launch_walk_step_ground(a1mpc_handle h, const a1mpc_walk_config& cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                    const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                    const double* foot_target, const double* ground, double* state_out, double* R_world_out, double* foot_abs_out,
+                                    double* foot_vel_body_out, uint8_t* touch_out, hipStream_t s) {
+    WalkGroundArgs g;
+    WalkArgs& w = g.w;
+    PlantArgs& a = w.p;
+    a.n = n; a.stride = state_stride; a.substeps = cfg.plant.substeps; a.dt = cfg.plant.dt; a.gravity = cfg.plant.gravity_z; a.mass = h->cfg.mass;
+    for (int i = 0; i < 9; ++i) a.inertia[i] = h->cfg.inertia_body[i];
+    a.state = state_in; a.R = R_world; a.foot = foot_abs; a.grf = grf_body; a.ext = ext_wrench; a.contacts = contacts;
+    a.state_out = state_out; a.R_out = R_world_out; a.foot_out = foot_abs_out;
+    const bool track = cfg.swing_track != 0.0;   // (-0 is no tracking either)
+    w.track = track ? cfg.swing_track : 0.0;
+    w.ground_z = ground ? 0.0 : cfg.ground_z; w.flat_ground = ground ? 0 : cfg.flat_ground;   // (with `ground` given cfg's plane is not read)
+    w.Rz = track ? R_z : nullptr; w.target = track ? foot_target : nullptr; w.vel_out = foot_vel_body_out;
+    g.ground = ground; g.touch = touch_out;
+    hipLaunchKernelGGL(a1mpc_walk_step_ground_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, g);
+}
+a1mpc_status a1mpc_ground_step_batch_device(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                                 const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                                 const double* d_ext_wrench, const double* d_R_z, const double* d_foot_target, const double* d_ground,
+                                                 double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, double* d_foot_vel_body_out, uint8_t* d_touch_out,
+                                                 void* hip_stream) {
+    if (const char* bad = invalid_walk_step_ground(h, cfg, n, d_state_in, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_R_z, d_foot_target, d_ground,
+                                                   d_state_out, d_R_world_out, d_foot_abs_out, d_foot_vel_body_out, d_touch_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_walk_step_ground(h, *cfg, n, d_state_in, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_ext_wrench, d_R_z, d_foot_target, d_ground,
+                                            d_state_out, d_R_world_out, d_foot_abs_out, d_foot_vel_body_out, d_touch_out, s));
+    return A1MPC_OK;
+}
+// the host-pointer entry: staged like a1mpc_walk_step_batch
+a1mpc_status a1mpc_ground_step_batch(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                          const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                          const double* foot_target, const double* ground, double* state_out, double* R_world_out, double* foot_abs_out,
+                                          double* foot_vel_body_out, uint8_t* touch_out) {
+    if (const char* bad = invalid_walk_step_ground(h, cfg, n, state_in, state_stride, R_world, foot_abs, grf_body, contacts, R_z, foot_target, ground, state_out,
+                                                   R_world_out, foot_abs_out, foot_vel_body_out, touch_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const size_t W = static_cast<size_t>(state_stride);
+    const bool track = cfg->swing_track != 0.0;
+    double *d_state = sg.in(state_in, W), *d_R = sg.in(R_world, 9), *d_foot = sg.in(foot_abs, 12);
+    const double *d_grf = sg.in(grf_body, 12), *d_ext = ext_wrench ? sg.in(ext_wrench, 6) : nullptr;
+    const double *d_Rz = track ? sg.in(R_z, 9) : nullptr, *d_tg = track ? sg.in(foot_target, 12) : nullptr, *d_gr = ground ? sg.in(ground, 3) : nullptr;
+    const uint8_t* d_ct = sg.in(contacts, 4);
+    double* d_out = (W == 12 || state_out == state_in) ? d_state : sg.in(static_cast<const double*>(state_out), W);
+    double* d_vel = sg.out(foot_vel_body_out, 12);
+    uint8_t* d_touch = sg.out(touch_out, 4);
+    sg.back(state_out, d_out, W); sg.back(R_world_out, d_R, 9); sg.back(foot_abs_out, d_foot, 12);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_walk_step_ground(h, *cfg, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_Rz, d_tg, d_gr, d_out, d_R, d_foot, d_vel, d_touch, s));
+    return sg.finish();
+}
+static const char* invalid_touch_force(double touch_force) {
+    return std::isfinite(touch_force) && touch_force >= 0.0 ? nullptr : "touch_force must be finite and not negative";
+}
+static void launch_walk_sensors_touch(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                      const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* foot_vel_body, const uint8_t* touch,
+                                      double touch_force, const double* rho_fix, const double* rho_opt, double* quat_out, double* imu_acc_raw_out, double* imu_gyro_raw_out,
+                                      double* joint_pos_out, double* joint_vel_out, double* foot_force_out, uint8_t* reach_out, double* foot_pos_rel_out,
+                                      double* foot_vel_rel_out, hipStream_t s) {
+    WalkTouchArgs t;
+    SynthArgs& a = t.w.s;
+    a.n = n; a.stride = state_stride; a.mass = h->cfg.mass;
+    std::memcpy(a.rho_fix, rho_fix, sizeof a.rho_fix); std::memcpy(a.rho_opt, rho_opt, sizeof a.rho_opt);
+    a.state = state; a.R = R_world; a.foot = foot_abs; a.grf = grf_body; a.ext = ext_wrench; a.contacts = contacts;
+    a.quat = quat_out; a.acc = imu_acc_raw_out; a.gyro = imu_gyro_raw_out; a.jpos = joint_pos_out; a.jvel = joint_vel_out; a.fforce = foot_force_out;
+    a.prel = foot_pos_rel_out; a.vrel = foot_vel_rel_out; a.reach = reach_out;
+    t.w.vel = foot_vel_body; t.touch = touch; t.touch_force = touch_force == 0.0 ? 0.0 : touch_force;   // (-0 reports +0, the walk sensors' bits)
+    hipLaunchKernelGGL(a1mpc_walk_sensors_touch_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, t);
+}
+a1mpc_status a1mpc_touch_sensors_batch_device(a1mpc_handle h, int32_t n, const double* d_state, int32_t state_stride, const double* d_R_world, const double* d_foot_abs,
+                                                   const double* d_grf_body, const uint8_t* d_contacts, const double* d_ext_wrench, const double* d_foot_vel_body,
+                                                   const uint8_t* d_touch, double touch_force, const double* rho_fix, const double* rho_opt, double* d_quat_out,
+                                                   double* d_imu_acc_raw_out, double* d_imu_gyro_raw_out, double* d_joint_pos_out, double* d_joint_vel_out,
+                                                   double* d_foot_force_out, uint8_t* d_reach_out, double* d_foot_pos_rel_out, double* d_foot_vel_rel_out, void* hip_stream) {
+    const char* bad = invalid_sensor_synthesis(h, n, d_state, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, rho_fix, rho_opt, d_quat_out, d_imu_acc_raw_out,
+                                               d_imu_gyro_raw_out, d_joint_pos_out, d_joint_vel_out, d_foot_force_out, d_reach_out);
+    if (!bad) bad = invalid_touch_force(touch_force);
+    if (bad) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_walk_sensors_touch(h, n, d_state, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_ext_wrench, d_foot_vel_body, d_touch, touch_force,
+                                              rho_fix, rho_opt, d_quat_out, d_imu_acc_raw_out, d_imu_gyro_raw_out, d_joint_pos_out, d_joint_vel_out, d_foot_force_out,
+                                              d_reach_out, d_foot_pos_rel_out, d_foot_vel_rel_out, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_touch_sensors_batch(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                            const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* foot_vel_body, const uint8_t* touch,
+                                            double touch_force, const double* rho_fix, const double* rho_opt, double* quat_out, double* imu_acc_raw_out,
+                                            double* imu_gyro_raw_out, double* joint_pos_out, double* joint_vel_out, double* foot_force_out, uint8_t* reach_out,
+                                            double* foot_pos_rel_out, double* foot_vel_rel_out) {
+    const char* bad = invalid_sensor_synthesis(h, n, state, state_stride, R_world, foot_abs, grf_body, contacts, rho_fix, rho_opt, quat_out, imu_acc_raw_out,
+                                               imu_gyro_raw_out, joint_pos_out, joint_vel_out, foot_force_out, reach_out);
+    if (!bad) bad = invalid_touch_force(touch_force);
+    if (bad) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const double *d_state = sg.in(state, static_cast<size_t>(state_stride)), *d_R = sg.in(R_world, 9), *d_foot = sg.in(foot_abs, 12), *d_grf = sg.in(grf_body, 12);
+    const double *d_ext = ext_wrench ? sg.in(ext_wrench, 6) : nullptr, *d_vel = foot_vel_body ? sg.in(foot_vel_body, 12) : nullptr;
+    const uint8_t *d_ct = sg.in(contacts, 4), *d_touch = touch ? sg.in(touch, 4) : nullptr;
+    double *d_quat = sg.out(quat_out, 4), *d_acc = sg.out(imu_acc_raw_out, 3), *d_gyro = sg.out(imu_gyro_raw_out, 3), *d_jp = sg.out(joint_pos_out, 12);
+    double *d_jv = sg.out(joint_vel_out, 12), *d_ff = sg.out(foot_force_out, 4), *d_pr = sg.out(foot_pos_rel_out, 12), *d_vr = sg.out(foot_vel_rel_out, 12);
+    uint8_t* d_reach = sg.out(reach_out, 4);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_walk_sensors_touch(h, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_vel, d_touch, touch_force, rho_fix, rho_opt, d_quat, d_acc,
+                                              d_gyro, d_jp, d_jv, d_ff, d_reach, d_pr, d_vr, s));
     return sg.finish();
 }
 #undef A1_STAGE_BEGIN

@@ -93,7 +93,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_walk_config", "a1mpc_walk_step_batch", "a1mpc_walk_step_batch_device", "a1mpc_walk_sensors_batch", "a1mpc_walk_sensors_batch_device",
+EXPORTS = ["a1mpc_ground_step_batch", "a1mpc_ground_step_batch_device", "a1mpc_touch_sensors_batch", "a1mpc_touch_sensors_batch_device",
+           "a1mpc_default_walk_config", "a1mpc_walk_step_batch", "a1mpc_walk_step_batch_device", "a1mpc_walk_sensors_batch", "a1mpc_walk_sensors_batch_device",
            "a1mpc_sensor_synthesis_batch", "a1mpc_sensor_synthesis_batch_device", "a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
            "a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
            "a1mpc_command_batch", "a1mpc_command_batch_device", "a1mpc_control_tick_sensors_device", "a1mpc_balance_wrench_kp_batch", "a1mpc_balance_wrench_kp_batch_device",
@@ -235,6 +236,14 @@ def load_library(path=None):
         lib.a1mpc_walk_step_batch_device.argtypes = [vp, C.POINTER(WalkConfig), i32, vpp, i32] + [vpp] * 11 + [vpp]; lib.a1mpc_walk_step_batch_device.restype = C.c_int
         lib.a1mpc_walk_sensors_batch.argtypes = [vp, i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, dp] + [dp] * 6 + [u8p, dp, dp]; lib.a1mpc_walk_sensors_batch.restype = C.c_int
         lib.a1mpc_walk_sensors_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 6 + [dp, dp] + [vpp] * 9 + [vpp]; lib.a1mpc_walk_sensors_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_ground_step_batch"):   # (sloped ground and sensed touchdowns; an older build bound by hand for an A/B lacks them)
+        lib.a1mpc_ground_step_batch.argtypes = [vp, C.POINTER(WalkConfig), i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, dp, dp, dp, dp, dp, u8p]
+        lib.a1mpc_ground_step_batch.restype = C.c_int
+        lib.a1mpc_ground_step_batch_device.argtypes = [vp, C.POINTER(WalkConfig), i32, vpp, i32] + [vpp] * 13 + [vpp]; lib.a1mpc_ground_step_batch_device.restype = C.c_int
+        lib.a1mpc_touch_sensors_batch.argtypes = [vp, i32, dp, i32, dp, dp, dp, u8p, dp, dp, u8p, C.c_double, dp, dp] + [dp] * 6 + [u8p, dp, dp]
+        lib.a1mpc_touch_sensors_batch.restype = C.c_int
+        lib.a1mpc_touch_sensors_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 7 + [C.c_double, dp, dp] + [vpp] * 9 + [vpp]
+        lib.a1mpc_touch_sensors_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -654,6 +663,65 @@ class Engine:
                                                       _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach), _dev(d_foot_pos_rel), _dev(d_foot_vel_rel),
                                                       C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_walk_sensors_batch_device")
+
+    # ---- sloped ground and sensed touchdowns: a ground plane per robot under the walk step, a touch sensor on the feet of the walk sensors ----
+    def walk_step_ground(self, state, R, foot, grf, contacts, R_z=None, foot_target=None, ground=None, ext_wrench=None, walk=None):
+        """walk_step's dict and touch (n, 4) uint8: a1mpc_ground_step_batch.  ground (n, 3) = (z0, sx, sy) per robot, the plane (z0 + sx X) + sy Y of the world, or
+        None (the walk config's own plane, or none); touch is 1 on a stance leg and on a swing leg the ground stopped"""
+        wc = self.walk_config() if walk is None else walk
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6)); gr = None if ground is None else _f64(ground, (n, 3))
+        Rz = None if R_z is None else _f64(R_z, (n, 9)); tg = None if foot_target is None else _f64(foot_target, (n, 12))
+        state_out = state.copy(); R_out = np.zeros((n, 9)); foot_out = np.zeros((n, 12)); vel_out = np.zeros((n, 12)); touch = np.zeros((n, 4), np.uint8)
+        rc = self.lib.a1mpc_ground_step_batch(self._h, C.byref(wc), n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(Rz), _dp(tg), _dp(gr),
+                                                   _dp(state_out), _dp(R_out), _dp(foot_out), _dp(vel_out), _u8p(touch))
+        _check(self.lib, rc, "a1mpc_ground_step_batch")
+        return dict(state=state_out, R=R_out, foot=foot_out, foot_vel_body=vel_out, touch=touch)
+
+    def walk_step_ground_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_R_z, d_foot_target, d_foot_vel_body, d_touch, d_ground=None,
+                                d_ext_wrench=None, d_state_out=None, d_R_out=None, d_foot_out=None, walk=None, stream=None):
+        """walk_step_device with d_ground (n, 3; None: the walk config's plane) and d_touch (n, 4 bytes, written)"""
+        wc = self.walk_config() if walk is None else walk
+        out = lambda o, i: _dev(i if o is None else o)
+        rc = self.lib.a1mpc_ground_step_batch_device(self._h, C.byref(wc), int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf),
+                                                          _dev(d_contacts), _dev(d_ext_wrench), _dev(d_R_z), _dev(d_foot_target), _dev(d_ground), out(d_state_out, d_state),
+                                                          out(d_R_out, d_R), out(d_foot_out, d_foot), _dev(d_foot_vel_body), _dev(d_touch),
+                                                          C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_ground_step_batch_device")
+
+    def walk_sensors_touch(self, state, R, foot, grf, contacts, foot_vel_body=None, touch=None, touch_force=0.0, ext_wrench=None, rho_fix=None, rho_opt=None,
+                           want_foot_rel=True):
+        """walk_sensors' dict: a1mpc_touch_sensors_batch.  touch (n, 4) bytes or None: a swing leg with a non-zero byte reports touch_force as its foot force"""
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        tc = None if touch is None else np.ascontiguousarray(touch, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6)); vel = None if foot_vel_body is None else _f64(foot_vel_body, (n, 12))
+        fix = _f64(self.A1_RHO_FIX if rho_fix is None else rho_fix, (4, 5)); opt = _f64(np.zeros((4, 3)) if rho_opt is None else rho_opt, (4, 3))
+        out = dict(quat=np.zeros((n, 4)), imu_acc_raw=np.zeros((n, 3)), imu_gyro_raw=np.zeros((n, 3)), joint_pos=np.zeros((n, 12)), joint_vel=np.zeros((n, 12)),
+                   foot_force=np.zeros((n, 4)), reach=np.zeros((n, 4), np.uint8), foot_pos_rel=np.zeros((n, 12)) if want_foot_rel else None,
+                   foot_vel_rel=np.zeros((n, 12)) if want_foot_rel else None)
+        rc = self.lib.a1mpc_touch_sensors_batch(self._h, n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(vel),
+                                                     None if tc is None else _u8p(tc), float(touch_force), _dp(fix), _dp(opt), _dp(out["quat"]), _dp(out["imu_acc_raw"]),
+                                                     _dp(out["imu_gyro_raw"]), _dp(out["joint_pos"]), _dp(out["joint_vel"]), _dp(out["foot_force"]), _u8p(out["reach"]),
+                                                     _dp(out["foot_pos_rel"]), _dp(out["foot_vel_rel"]))
+        _check(self.lib, rc, "a1mpc_touch_sensors_batch")
+        return out
+
+    def walk_sensors_touch_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_joint_pos, d_joint_vel,
+                                  d_foot_force, d_reach, d_foot_pos_rel=None, d_foot_vel_rel=None, d_ext_wrench=None, d_foot_vel_body=None, d_touch=None, touch_force=0.0,
+                                  rho_fix=None, rho_opt=None, stream=None):
+        """walk_sensors_device with d_touch and touch_force: on the stream of the preceding walk_step_ground_device it reads that step's touch bytes"""
+        fix = _f64(self.A1_RHO_FIX if rho_fix is None else rho_fix, (4, 5)); opt = _f64(np.zeros((4, 3)) if rho_opt is None else rho_opt, (4, 3))
+        rc = self.lib.a1mpc_touch_sensors_batch_device(self._h, int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf), _dev(d_contacts),
+                                                            _dev(d_ext_wrench), _dev(d_foot_vel_body), _dev(d_touch), float(touch_force), _dp(fix), _dp(opt), _dev(d_quat),
+                                                            _dev(d_imu_acc_raw), _dev(d_imu_gyro_raw), _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach),
+                                                            _dev(d_foot_pos_rel), _dev(d_foot_vel_rel), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_touch_sensors_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

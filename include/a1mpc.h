@@ -858,6 +858,54 @@ a1mpc_status a1mpc_walk_sensors_batch_device(a1mpc_handle h, int32_t n, const do
                                              double* d_foot_pos_rel_out, double* d_foot_vel_rel_out, void* hip_stream);
 
 /*
+ * Sloped ground and sensed touchdowns for the walking plant: a ground plane PER ROBOT under a1mpc_walk_step_batch, and a touch sensor on the feet of
+ * a1mpc_walk_sensors_batch.  With them  a1mpc_touch_sensors_batch_device -> a1mpc_control_tick_sensors_device -> a1mpc_ground_step_batch_device  runs on one
+ * stream with no host copy, and the gait layer's terrain fit (compute_walking_surface, use_terrain_adapt) and its early-contact latch meet a slope and a touchdown they
+ * can be held to.  Kernels of their own (a1mpc_walk_step_ground_kernel, a1mpc_walk_sensors_touch_kernel): the four entries above are unchanged, and the walk family's
+ * exported symbols stay the five of its block -- these four are a family of their own, a1mpc_ground_* / a1mpc_touch_*.
+ *
+ * a1mpc_ground_step_batch is a1mpc_walk_step_batch with one more input after foot_target and one more output after foot_vel_body_out:
+ *   in   ground       n x 3, optional: (z0, sx, sy) of robot b; its ground is the plane hz(X, Y) = (z0 + sx X) + sy Y of the world, in that operation order, no FMA
+ *   after the last sub-step, for every leg, with ground given:  X = pos'_x + r'_x,  Y = pos'_y + r'_y,  gz = hz(X, Y) - pos'_z;  a stance foot gets r'_z = gz;  a swing
+ *        foot gets r'_z = (r'_z < gz) ? gz : r'_z.  The projection is VERTICAL: x and y of every foot and of the body do not change.  cfg->flat_ground and
+ *        cfg->ground_z are not read.  ground NULL: the rule of a1mpc_walk_step_batch with cfg's plane, or none
+ *   out  touch_out    n x 4 bytes, required: 1 for a stance leg; for a swing leg 1 exactly when the comparison above lifted the foot (the same comparison: a NaN
+ *                     gives 0); 0 for every swing leg when there is no ground at all (ground NULL and flat_ground == 0)
+ * Reductions: with ground NULL every other output is a1mpc_walk_step_batch's bit for bit; with ground = (ground_z, 0, 0) and finite inputs every other output is
+ * a1mpc_walk_step_batch's with flat_ground = 1, bit for bit.  A row of ground that is not finite stays with its robot (the z of its feet).
+ * Refused: everything a1mpc_walk_step_batch refuses (the ground_z check only with ground NULL), and a null touch_out.  In-place use of state, R_world and foot_abs
+ * follows a1mpc_walk_step_batch's rule.
+ *
+ * a1mpc_touch_sensors_batch is a1mpc_walk_sensors_batch with two more inputs after foot_vel_body: touch (n x 4 bytes, optional: the step's touch_out) and
+ * touch_force (by value).  On a SWING leg whose touch byte is non-zero foot_force_l = touch_force, selected and not added; a stance leg's byte reaches no output.
+ * Nothing else changes: legs are massless and there is no impact, so the accelerometer is a1mpc_walk_sensors_batch's.  With touch NULL or touch_force == 0 every
+ * output is a1mpc_walk_sensors_batch's bit for bit.  Refused: everything a1mpc_walk_sensors_batch refuses, and a touch_force that is negative or not finite.
+ *
+ * What it is not: ONE plane per robot -- no steps, no height field; the projection is vertical, so a stance foot on a slope neither slips nor feels a friction cone;
+ * the touch force is a constant, not a contact model; nothing stops the BODY itself at the plane; and the tick's foot preview still plans flat-ground footholds.
+ */
+a1mpc_status a1mpc_ground_step_batch(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                          const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                          const double* foot_target, const double* ground, double* state_out, double* R_world_out, double* foot_abs_out,
+                                          double* foot_vel_body_out, uint8_t* touch_out);
+a1mpc_status a1mpc_ground_step_batch_device(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                                 const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                                 const double* d_ext_wrench, const double* d_R_z, const double* d_foot_target, const double* d_ground,
+                                                 double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, double* d_foot_vel_body_out, uint8_t* d_touch_out,
+                                                 void* hip_stream);
+a1mpc_status a1mpc_touch_sensors_batch(a1mpc_handle h, int32_t n, const double* state, int32_t state_stride, const double* R_world, const double* foot_abs,
+                                            const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* foot_vel_body, const uint8_t* touch,
+                                            double touch_force, const double* rho_fix, const double* rho_opt, double* quat_out, double* imu_acc_raw_out,
+                                            double* imu_gyro_raw_out, double* joint_pos_out, double* joint_vel_out, double* foot_force_out, uint8_t* reach_out,
+                                            double* foot_pos_rel_out, double* foot_vel_rel_out);
+a1mpc_status a1mpc_touch_sensors_batch_device(a1mpc_handle h, int32_t n, const double* d_state, int32_t state_stride, const double* d_R_world, const double* d_foot_abs,
+                                                   const double* d_grf_body, const uint8_t* d_contacts, const double* d_ext_wrench, const double* d_foot_vel_body,
+                                                   const uint8_t* d_touch, double touch_force, const double* rho_fix, const double* rho_opt, double* d_quat_out,
+                                                   double* d_imu_acc_raw_out, double* d_imu_gyro_raw_out, double* d_joint_pos_out, double* d_joint_vel_out,
+                                                   double* d_foot_force_out, uint8_t* d_reach_out, double* d_foot_pos_rel_out, double* d_foot_vel_rel_out,
+                                                   void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
