@@ -1617,6 +1617,118 @@ __global__ __launch_bounds__(64) void a1mpc_walk_sensors_touch_kernel(const Walk
 #undef A1_PL_MV
 #undef A1_PL_MTV
 
+// ---- sensor noise and IMU bias (a1mpc_sensor_noise_batch): white Gaussian noise on the six sensor arrays of the synthesis kernels above, IN PLACE, and a random-walk
+// bias on the IMU.  The generator is counter-based: draw j = 0 .. 21 of the robot with global index g at `tick` is Philox4x32-10 on the counter (j, g, tick low, tick
+// high) under the key (seed low, seed high), its four words give two uniforms of 52 bits and Box-Muller makes two unit normals z[2j], z[2j + 1] of them; so a robot's 44
+// normals are a function of (seed, g, tick) alone, whatever the batch, the robot's place in it and the lane that computes them.  z: [0:3) gyro, [3:6) acc, [6:9) gyro
+// bias step, [9:12) acc bias step, [12:15) attitude, [15] unused, [16:28) joint angles, [28:40) joint rates, [40:44) foot forces.
+// Lanes: 16 robots per wavefront, four lanes per robot as above.  Lane l computes the draws l, l + 4, ... into the wave's LDS image of z (a draw no channel reads is
+// skipped and its two slots hold +0: `draws` is the launcher's mask); then lane l applies leg l's joint and force noise, lanes 0 .. 2 one IMU axis each (bias, gyro,
+// acc), lane 3 the quaternion.  A sigma of 0 SELECTS the input (nothing is added: -0 and NaN payloads keep their bits); no FMA contraction, sums left to right
+constexpr int kNoiseZ = 44, kNoiseDraws = 22;
+struct NoiseArgs {
+    int32_t n;
+    uint32_t draws;              // bit j: draw j is computed
+    uint32_t key0, key1;         // the seed's words
+    uint32_t tick_lo, tick_hi;
+    uint64_t robot0;             // robot0 + n <= 2^32
+    double gyro_sigma, acc_sigma, gyro_walk, acc_walk, att_sigma, jpos_sigma, jvel_sigma, fforce_sigma;   // (a sigma whose array is null arrives as 0)
+    double *quat, *acc, *gyro, *jpos, *jvel, *fforce;   // in place; each may be null
+    double* bias;                // n x 6 in / out, may be null
+    double* z;                   // n x 44, may be null
+};
+__device__ __forceinline__ void noise_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * c0, p1 = static_cast<uint64_t>(0xCD9E8D57u) * c2;
+        const uint32_t n0 = static_cast<uint32_t>(p1 >> 32) ^ c1 ^ k0, n2 = static_cast<uint32_t>(p0 >> 32) ^ c3 ^ k1;
+        c1 = static_cast<uint32_t>(p1); c3 = static_cast<uint32_t>(p0); c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;   // (the bump after the tenth round is not used)
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__global__ __launch_bounds__(64) void a1mpc_sensor_noise_kernel(const NoiseArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double zl[16 * kNoiseZ];
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    const uint32_t g = static_cast<uint32_t>(a.robot0 + static_cast<uint64_t>(b));
+    double* const zr = zl + q * kNoiseZ;
+    if (alive) {
+#pragma unroll
+        for (int m = 0; m < 6; ++m) {
+            const int j = l + 4 * m;
+            if (j >= kNoiseDraws) continue;
+            double z0 = 0.0, z1 = 0.0;
+            if ((a.draws >> j) & 1u) {   // (the same in every lane of a given l: the mask is the launch's)
+                uint32_t x[4];
+                noise_philox(static_cast<uint32_t>(j), g, a.tick_lo, a.tick_hi, a.key0, a.key1, x);
+                const uint64_t k1 = (static_cast<uint64_t>(x[0] >> 6) << 26) | (x[1] >> 6), k2 = (static_cast<uint64_t>(x[2] >> 6) << 26) | (x[3] >> 6);
+                const double u1 = (static_cast<double>(k1) + 0.5) * 0x1p-52, u2 = (static_cast<double>(k2) + 0.5) * 0x1p-52;   // exact, in (0, 1)
+                const double r = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
+                z0 = r * cos(ang); z1 = r * sin(ang);
+            }
+            zr[2 * j] = z0; zr[2 * j + 1] = z1;
+        }
+    }
+    WaveStage::sync();
+    if (alive) {
+        if (a.jpos_sigma != 0.0) {
+            double* x = a.jpos + b * 12 + 3 * l;
+            const double *z = zr + 16 + 3 * l, v0 = x[0], v1 = x[1], v2 = x[2];
+            x[0] = v0 + a.jpos_sigma * z[0]; x[1] = v1 + a.jpos_sigma * z[1]; x[2] = v2 + a.jpos_sigma * z[2];
+        }
+        if (a.jvel_sigma != 0.0) {
+            double* x = a.jvel + b * 12 + 3 * l;
+            const double *z = zr + 28 + 3 * l, v0 = x[0], v1 = x[1], v2 = x[2];
+            x[0] = v0 + a.jvel_sigma * z[0]; x[1] = v1 + a.jvel_sigma * z[1]; x[2] = v2 + a.jvel_sigma * z[2];
+        }
+        if (a.fforce_sigma != 0.0) { double* x = a.fforce + b * 4 + l; x[0] = x[0] + a.fforce_sigma * zr[40 + l]; }
+        if (l < 3) {
+            // one IMU axis: the bias walks first and is stored back, then the sample is (raw + bias) + sigma z; a walk of 0 leaves the bias's bits alone
+            double bg = 0.0, ba = 0.0;
+            if (a.bias) {
+                double* pb = a.bias + b * 6;
+                bg = pb[l]; ba = pb[3 + l];
+                if (a.gyro_walk != 0.0) { bg = bg + a.gyro_walk * zr[6 + l]; pb[l] = bg; }
+                if (a.acc_walk != 0.0) { ba = ba + a.acc_walk * zr[9 + l]; pb[3 + l] = ba; }
+            }
+            if (a.gyro && (a.bias || a.gyro_sigma != 0.0)) {
+                double v = a.gyro[b * 3 + l];
+                if (a.bias) v = v + bg;
+                if (a.gyro_sigma != 0.0) v = v + a.gyro_sigma * zr[l];
+                a.gyro[b * 3 + l] = v;
+            }
+            if (a.acc && (a.bias || a.acc_sigma != 0.0)) {
+                double v = a.acc[b * 3 + l];
+                if (a.bias) v = v + ba;
+                if (a.acc_sigma != 0.0) v = v + a.acc_sigma * zr[3 + l];
+                a.acc[b * 3 + l] = v;
+            }
+        } else if (a.att_sigma != 0.0) {
+            // a small rotation in the body frame: q (x) (1, theta / 2), w first, normalised
+            double* pq = a.quat + b * 4;
+            const double w = pq[0], x = pq[1], y = pq[2], z = pq[3];
+            const double dx = (a.att_sigma * zr[12]) * 0.5, dy = (a.att_sigma * zr[13]) * 0.5, dz = (a.att_sigma * zr[14]) * 0.5;
+            const double nw = ((w - x * dx) - y * dy) - z * dz, nx = ((x + w * dx) + y * dz) - z * dy;
+            const double ny = ((y + w * dy) + z * dx) - x * dz, nz = ((z + w * dz) + x * dy) - y * dx;
+            const double nrm = sqrt(((nw * nw + nx * nx) + ny * ny) + nz * nz);
+            pq[0] = nw / nrm; pq[1] = nx / nrm; pq[2] = ny / nrm; pq[3] = nz / nrm;
+        }
+    }
+    if (a.z) {
+        double* oz = a.z + first * kNoiseZ;
+        const int cz = live * kNoiseZ;
+#pragma unroll
+        for (int m = 0; m < 11; ++m) { const int e = lane + 64 * m; if (e < cz) oz[e] = zl[e]; }
+    }
+}
+
 thread_local std::string g_last_error;
 std::mutex g_cache_mu;
 thread_local bool g_clk_ran = false;
@@ -4576,6 +4688,80 @@ a1mpc_status a1mpc_touch_sensors_batch(a1mpc_handle h, int32_t n, const double* 
     A1_STAGED(sg);
     A1_STAGE_LAUNCH(launch_walk_sensors_touch(h, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_vel, d_touch, touch_force, rho_fix, rho_opt, d_quat, d_acc,
                                               d_gyro, d_jp, d_jv, d_ff, d_reach, d_pr, d_vr, s));
+    return sg.finish();
+}
+// ---- sensor noise and IMU bias behind the C ABI: a1mpc_sensor_noise_kernel, no handle state
+void a1mpc_default_noise_config(a1mpc_noise_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof *c);   // seed 0 and every sigma +0: off
+}
+// what the two entries refuse, or null (all before the first HIP call).  arr: quat, imu_acc_raw, imu_gyro_raw, joint_pos, joint_vel, foot_force, imu_bias, z_out
+constexpr size_t kNoiseWidths[8] = {4, 3, 3, 12, 12, 4, 6, kNoiseZ};
+static const char* invalid_sensor_noise(a1mpc_handle h, const a1mpc_noise_config* cfg, int32_t n, uint64_t robot0, const double* const* arr) {
+    if (!h) return "null handle";
+    if (!cfg) return "null a1mpc_noise_config";
+    if (n < 0) return "negative n";
+    const struct { double v; const char* what; } levels[8] = {
+        {cfg->gyro_sigma, "a1mpc_noise_config.gyro_sigma must be finite and not negative"}, {cfg->acc_sigma, "a1mpc_noise_config.acc_sigma must be finite and not negative"},
+        {cfg->gyro_bias_walk, "a1mpc_noise_config.gyro_bias_walk must be finite and not negative"},
+        {cfg->acc_bias_walk, "a1mpc_noise_config.acc_bias_walk must be finite and not negative"}, {cfg->att_sigma, "a1mpc_noise_config.att_sigma must be finite and not negative"},
+        {cfg->joint_pos_sigma, "a1mpc_noise_config.joint_pos_sigma must be finite and not negative"},
+        {cfg->joint_vel_sigma, "a1mpc_noise_config.joint_vel_sigma must be finite and not negative"},
+        {cfg->foot_force_sigma, "a1mpc_noise_config.foot_force_sigma must be finite and not negative"}};
+    for (const auto& lv : levels)
+        if (!std::isfinite(lv.v) || lv.v < 0.0) return lv.what;
+    if ((cfg->gyro_bias_walk > 0.0 || cfg->acc_bias_walk > 0.0) && !arr[6]) return "null imu_bias with a bias walk > 0";
+    if (robot0 > (uint64_t{1} << 32) - static_cast<uint64_t>(n)) return "robot0 + n beyond 2^32";
+    for (int i = 0; i < 8; ++i)
+        for (int k = i + 1; k < 8; ++k) {
+            if (!arr[i] || !arr[k]) continue;
+            const uintptr_t pi = reinterpret_cast<uintptr_t>(arr[i]), pk = reinterpret_cast<uintptr_t>(arr[k]);
+            const uintptr_t bi = static_cast<uintptr_t>(n) * kNoiseWidths[i] * sizeof(double), bk = static_cast<uintptr_t>(n) * kNoiseWidths[k] * sizeof(double);
+            if (pi < pk + bk && pk < pi + bi) return "two of the arrays overlap";
+        }
+    return nullptr;
+}
+static void launch_sensor_noise(const a1mpc_noise_config& cfg, int32_t n, uint64_t robot0, uint64_t tick, double* quat, double* imu_acc_raw, double* imu_gyro_raw,
+                                double* joint_pos, double* joint_vel, double* foot_force, double* imu_bias, double* z_out, hipStream_t s) {
+    NoiseArgs a;
+    a.n = n; a.key0 = static_cast<uint32_t>(cfg.seed); a.key1 = static_cast<uint32_t>(cfg.seed >> 32);
+    a.tick_lo = static_cast<uint32_t>(tick); a.tick_hi = static_cast<uint32_t>(tick >> 32); a.robot0 = robot0;
+    a.gyro_sigma = imu_gyro_raw ? cfg.gyro_sigma : 0.0; a.acc_sigma = imu_acc_raw ? cfg.acc_sigma : 0.0;
+    a.gyro_walk = imu_bias ? cfg.gyro_bias_walk : 0.0; a.acc_walk = imu_bias ? cfg.acc_bias_walk : 0.0;
+    a.att_sigma = quat ? cfg.att_sigma : 0.0; a.jpos_sigma = joint_pos ? cfg.joint_pos_sigma : 0.0; a.jvel_sigma = joint_vel ? cfg.joint_vel_sigma : 0.0;
+    a.fforce_sigma = foot_force ? cfg.foot_force_sigma : 0.0;
+    a.quat = quat; a.acc = imu_acc_raw; a.gyro = imu_gyro_raw; a.jpos = joint_pos; a.jvel = joint_vel; a.fforce = foot_force; a.bias = imu_bias; a.z = z_out;
+    // the draws somebody reads: all of them with z_out, else those of the channels that are on (z[2 j], z[2 j + 1] are draw j's)
+    uint64_t zs = 0;
+    const auto on = [&zs](double level, int z0, int count) { if (level != 0.0) zs |= ((uint64_t{1} << count) - 1) << z0; };
+    on(a.gyro_sigma, 0, 3); on(a.acc_sigma, 3, 3); on(a.gyro_walk, 6, 3); on(a.acc_walk, 9, 3); on(a.att_sigma, 12, 3); on(a.jpos_sigma, 16, 12); on(a.jvel_sigma, 28, 12);
+    on(a.fforce_sigma, 40, 4);
+    a.draws = 0;
+    for (int j = 0; j < kNoiseDraws; ++j)
+        if (z_out || ((zs >> (2 * j)) & 3u)) a.draws |= 1u << j;
+    hipLaunchKernelGGL(a1mpc_sensor_noise_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, a);
+}
+a1mpc_status a1mpc_sensor_noise_batch_device(a1mpc_handle h, const a1mpc_noise_config* cfg, int32_t n, uint64_t robot0, uint64_t tick, double* d_quat,
+                                             double* d_imu_acc_raw, double* d_imu_gyro_raw, double* d_joint_pos, double* d_joint_vel, double* d_foot_force,
+                                             double* d_imu_bias, double* d_z_out, void* hip_stream) {
+    const double* const arr[8] = {d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_joint_pos, d_joint_vel, d_foot_force, d_imu_bias, d_z_out};
+    if (const char* bad = invalid_sensor_noise(h, cfg, n, robot0, arr)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_sensor_noise(*cfg, n, robot0, tick, d_quat, d_imu_acc_raw, d_imu_gyro_raw, d_joint_pos, d_joint_vel, d_foot_force, d_imu_bias, d_z_out, s));
+    return A1MPC_OK;
+}
+// the host-pointer entry: every array the caller gives is staged in and back (in place on the staged copy), z_out back alone
+a1mpc_status a1mpc_sensor_noise_batch(a1mpc_handle h, const a1mpc_noise_config* cfg, int32_t n, uint64_t robot0, uint64_t tick, double* quat, double* imu_acc_raw,
+                                      double* imu_gyro_raw, double* joint_pos, double* joint_vel, double* foot_force, double* imu_bias, double* z_out) {
+    const double* const arr[8] = {quat, imu_acc_raw, imu_gyro_raw, joint_pos, joint_vel, foot_force, imu_bias, z_out};
+    if (const char* bad = invalid_sensor_noise(h, cfg, n, robot0, arr)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const auto io = [&sg](double* host, size_t w) { return host ? sg.inout(host, w) : nullptr; };
+    double *d_quat = io(quat, 4), *d_acc = io(imu_acc_raw, 3), *d_gyro = io(imu_gyro_raw, 3), *d_jp = io(joint_pos, 12), *d_jv = io(joint_vel, 12), *d_ff = io(foot_force, 4);
+    double *d_bias = io(imu_bias, 6), *d_z = sg.out(z_out, kNoiseZ);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_sensor_noise(*cfg, n, robot0, tick, d_quat, d_acc, d_gyro, d_jp, d_jv, d_ff, d_bias, d_z, s));
     return sg.finish();
 }
 #undef A1_STAGE_BEGIN

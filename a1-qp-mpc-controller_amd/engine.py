@@ -74,6 +74,13 @@ class WalkConfig(C.Structure):  # a1mpc_walk_config: the plant's configuration, 
     _fields_ = [("plant", PlantConfig), ("swing_track", C.c_double), ("flat_ground", C.c_int32), ("ground_z", C.c_double)]
 
 
+class NoiseConfig(C.Structure):  # a1mpc_noise_config: the generator's seed and the levels of the eight noise channels (0 = that channel is off)
+    _fields_ = [("seed", C.c_uint64), ("gyro_sigma", C.c_double), ("acc_sigma", C.c_double), ("gyro_bias_walk", C.c_double), ("acc_bias_walk", C.c_double),
+                ("att_sigma", C.c_double), ("joint_pos_sigma", C.c_double), ("joint_vel_sigma", C.c_double), ("foot_force_sigma", C.c_double)]
+
+
+NOISE_SENSORS = ("quat", "imu_acc_raw", "imu_gyro_raw", "joint_pos", "joint_vel", "foot_force")   # the arrays a1mpc_sensor_noise_batch works on in place, in its order
+NOISE_WIDTHS = dict(quat=4, imu_acc_raw=3, imu_gyro_raw=3, joint_pos=12, joint_vel=12, foot_force=4, imu_bias=6, z=44)
 TICK_SENSOR_POINTERS = ("quat", "imu_acc_raw", "imu_gyro_raw", "cmd", "mode_toggle", "body_height", "ctrl_state", "root_pos_d", "kp_linear_xy", "mpc_init_counter")
 COMMAND_STATE_FIELDS = ("body_height", "ctrl_state", "root_euler_d", "root_pos_d", "kp_linear_xy", "mpc_init_counter")   # carried by the caller, in the C ABI's order
 
@@ -93,7 +100,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_ground_step_batch", "a1mpc_ground_step_batch_device", "a1mpc_touch_sensors_batch", "a1mpc_touch_sensors_batch_device",
+EXPORTS = ["a1mpc_default_noise_config", "a1mpc_sensor_noise_batch", "a1mpc_sensor_noise_batch_device",
+           "a1mpc_ground_step_batch", "a1mpc_ground_step_batch_device", "a1mpc_touch_sensors_batch", "a1mpc_touch_sensors_batch_device",
            "a1mpc_default_walk_config", "a1mpc_walk_step_batch", "a1mpc_walk_step_batch_device", "a1mpc_walk_sensors_batch", "a1mpc_walk_sensors_batch_device",
            "a1mpc_sensor_synthesis_batch", "a1mpc_sensor_synthesis_batch_device", "a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
            "a1mpc_default_sensor_config", "a1mpc_default_command_config", "a1mpc_reset_sensor_state", "a1mpc_sensor_frontend_batch", "a1mpc_sensor_frontend_batch_device",
@@ -244,6 +252,11 @@ def load_library(path=None):
         lib.a1mpc_touch_sensors_batch.restype = C.c_int
         lib.a1mpc_touch_sensors_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 7 + [C.c_double, dp, dp] + [vpp] * 9 + [vpp]
         lib.a1mpc_touch_sensors_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_sensor_noise_batch"):   # (sensor noise and IMU bias; an older build bound by hand for an A/B lacks them)
+        u64 = C.c_uint64
+        lib.a1mpc_default_noise_config.argtypes = [C.POINTER(NoiseConfig)]; lib.a1mpc_default_noise_config.restype = None
+        lib.a1mpc_sensor_noise_batch.argtypes = [vp, C.POINTER(NoiseConfig), i32, u64, u64] + [dp] * 8; lib.a1mpc_sensor_noise_batch.restype = C.c_int
+        lib.a1mpc_sensor_noise_batch_device.argtypes = [vp, C.POINTER(NoiseConfig), i32, u64, u64] + [vpp] * 8 + [vpp]; lib.a1mpc_sensor_noise_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -722,6 +735,42 @@ class Engine:
                                                             _dev(d_imu_acc_raw), _dev(d_imu_gyro_raw), _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach),
                                                             _dev(d_foot_pos_rel), _dev(d_foot_vel_rel), C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_touch_sensors_batch_device")
+
+    # ---- sensor noise and IMU bias: counter-based Gaussian noise on the synthesised sensors, in place, the same bits for a robot and tick in every batch ----
+    def noise_config(self, **fields):
+        """a1mpc_default_noise_config (seed 0, every level 0: off) with `fields` overridden: seed, gyro_sigma, acc_sigma, gyro_bias_walk, acc_bias_walk, att_sigma,
+        joint_pos_sigma, joint_vel_sigma, foot_force_sigma"""
+        nc = NoiseConfig(); self.lib.a1mpc_default_noise_config(C.byref(nc))
+        for k, v in fields.items():
+            if not hasattr(nc, k):
+                raise KeyError(k)
+            setattr(nc, k, int(v) if k == "seed" else float(v))
+        return nc
+
+    def sensor_noise(self, noise, tick, quat=None, imu_acc_raw=None, imu_gyro_raw=None, joint_pos=None, joint_vel=None, foot_force=None, imu_bias=None, robot0=0, want_z=False):
+        """a1mpc_sensor_noise_batch: the sensor arrays given (C-contiguous float64, n rows each, the layouts of sensor_synthesis' dict) and imu_bias (n, 6) are changed IN
+        PLACE; robot0 is the global index of row 0 -> z (n, 44), the unit normals drawn, or None"""
+        arrs = dict(quat=quat, imu_acc_raw=imu_acc_raw, imu_gyro_raw=imu_gyro_raw, joint_pos=joint_pos, joint_vel=joint_vel, foot_force=foot_force, imu_bias=imu_bias)
+        given = {k: v for k, v in arrs.items() if v is not None}
+        if not given:
+            raise ValueError("sensor_noise needs one array at the least")
+        n = next(iter(given.values())).shape[0]
+        for k, v in given.items():
+            if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.flags.writeable and v.shape == (n, NOISE_WIDTHS[k])):
+                raise ValueError(f"{k} must be a writeable C-contiguous float64 array of shape ({n}, {NOISE_WIDTHS[k]}): it is changed in place")
+        z = np.zeros((n, NOISE_WIDTHS["z"])) if want_z else None
+        rc = self.lib.a1mpc_sensor_noise_batch(self._h, C.byref(noise), n, int(robot0), int(tick), *[_dp(arrs[k]) for k in NOISE_SENSORS], _dp(imu_bias), _dp(z))
+        _check(self.lib, rc, "a1mpc_sensor_noise_batch")
+        return z
+
+    def sensor_noise_device(self, noise, n, tick, d_quat=None, d_imu_acc_raw=None, d_imu_gyro_raw=None, d_joint_pos=None, d_joint_vel=None, d_foot_force=None, d_imu_bias=None,
+                            d_z=None, robot0=0, stream=None):
+        """device pointers (torch tensors), asynchronous on `stream`, in place: behind walk_sensors_device (or either of its siblings) and in front of
+        control_tick_sensors_device on one stream it puts noise on that tick's sensors; tick and robot0 are passed by value"""
+        rc = self.lib.a1mpc_sensor_noise_batch_device(self._h, C.byref(noise), int(n), int(robot0), int(tick), _dev(d_quat), _dev(d_imu_acc_raw), _dev(d_imu_gyro_raw),
+                                                      _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_imu_bias), _dev(d_z),
+                                                      C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_sensor_noise_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

@@ -786,7 +786,8 @@ a1mpc_status a1mpc_plant_step_batch_device(a1mpc_handle h, const a1mpc_plant_con
  *   reach flags    reach_l bit 0: dy dy + p2 p2 < L L was clamped; bit 1: c was clamped.  Any bit set: this leg's joint_vel is exactly +0
  * Arithmetic: contraction off, no fused multiply-add; IEEE +, -, *, / and sqrt, the device library's atan2, acos, sin and cos.  Each robot's outputs are a pure function
  * of that robot's inputs alone: the same bits at every batch size, position in the batch and entry.
- * What it is not: no sensor noise or bias, no ground or contact model (foot_force is the applied force, not a measured one); a swing foot is fixed in the body, as the
+ * What it is not: no sensor noise or bias of its own (a1mpc_sensor_noise_batch below adds them to these outputs), no ground or contact model (foot_force is the
+ * applied force, not a measured one); a swing foot is fixed in the body, as the
  * plant keeps it, so the loop this closes is the standing robot.
  * out: quat_out n x 4, imu_acc_raw_out and imu_gyro_raw_out n x 3, joint_pos_out and joint_vel_out n x 12, foot_force_out n x 4 doubles and reach_out n x 4 bytes, all
  * required; foot_pos_rel_out and foot_vel_rel_out n x 12, optional (NULL = not wanted).  No output may alias an input.  Non-finite inputs of one robot stay with that robot.
@@ -904,6 +905,55 @@ a1mpc_status a1mpc_touch_sensors_batch_device(a1mpc_handle h, int32_t n, const d
                                                    double* d_imu_acc_raw_out, double* d_imu_gyro_raw_out, double* d_joint_pos_out, double* d_joint_vel_out,
                                                    double* d_foot_force_out, uint8_t* d_reach_out, double* d_foot_pos_rel_out, double* d_foot_vel_rel_out,
                                                    void* hip_stream);
+
+/*
+ * Sensor noise and IMU bias on the device, reproducible per robot and tick: white Gaussian noise on the six sensor arrays that a1mpc_sensor_synthesis_batch,
+ * a1mpc_walk_sensors_batch and a1mpc_touch_sensors_batch write, and a random-walk bias on the IMU.  With it  a1mpc_walk_sensors_batch_device ->
+ * a1mpc_sensor_noise_batch_device -> a1mpc_control_tick_sensors_device -> a1mpc_walk_step_batch_device  runs on one stream with no host copy, and the EKF's
+ * covariances, the contact logic's force thresholds and the IMU window meet inputs that are not exact.  A kernel of its own (a1mpc_sensor_noise_kernel) and a family
+ * of its own, a1mpc_*noise*: the entries above are unchanged.
+ *
+ * in / out (all optional, NULL = that sensor is left alone), modified IN PLACE, in the synthesis entries' layouts: quat n x 4 (w first), imu_acc_raw and imu_gyro_raw
+ *        n x 3, joint_pos and joint_vel n x 12, foot_force n x 4
+ *        imu_bias  n x 6, optional: (gyro bias, acc bias) of robot b, carried by the caller from call to call (start it at zero); the handle gets no state
+ * out    z_out     n x 44, optional: the unit normals drawn for robot b, the injected noise's truth
+ * by value: robot0, the global index of row 0 (robot b of the call is robot g = robot0 + b of the experiment), and tick
+ * Generator, per robot: draw j = 0 .. 21 is Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with the key (seed low word,
+ * seed high word) on the counter (j, g, tick low word, tick high word).  Of its four words x0 .. x3:
+ *        k1 = (x0 >> 6) 2^26 + (x1 >> 6),  k2 = (x2 >> 6) 2^26 + (x3 >> 6),  u = (k + 0.5) 2^-52   (exact, in (0, 1))
+ *        r = sqrt(-2 log u1),  a = 6.283185307179586 u2,  z[2 j] = r cos a,  z[2 j + 1] = r sin a
+ * Channels: z[0:3) gyro, z[3:6) acc, z[6:9) gyro bias step, z[9:12) acc bias step, z[12:15) attitude, z[15] unused, z[16:28) joint_pos, z[28:40) joint_vel,
+ * z[40:44) foot_force.  A robot's normals are a function of (seed, g, tick) alone: the same bits at every batch size, position in the batch, shard and entry, and the
+ * same whatever the sigmas are.
+ * Arithmetic (contraction off, no fused multiply-add, sums left to right):
+ *   bias      b' = b + walk z, stored back; a walk of 0 leaves b's bits alone and still applies it
+ *   IMU       gyro' = (gyro + b'_gyro) + gyro_sigma z, acc likewise; without imu_bias there is no bias term
+ *   attitude  theta = att_sigma z[12:15),  dq = (1, theta / 2),  q' = q (x) dq (Hamilton product, w first: a small rotation in the body frame), every component
+ *             divided by sqrt(((w w + x x) + y y) + z z)
+ *   joints and forces  x' = x + sigma z, on every leg, stance or swing
+ * A sigma of 0 SELECTS the input: nothing is added (-0 and NaN payloads keep their bits; the quaternion is not renormalised) and that channel's draws are skipped
+ * unless z_out asks for them.  A non-finite input of one robot stays with that robot.
+ * What it is not: white Gaussian noise and a random-walk bias only -- no quantisation, no latency, no dropout, no temperature or scale-factor model, no correlation
+ * between channels or in time; and the bias is not estimated by anything: the tick's EKF has no bias states, so it sees the bias as a constant error.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch, every array left untouched: a null handle or cfg, n < 0, a sigma or
+ * walk that is negative or not finite, a walk > 0 with imu_bias NULL, robot0 + n > 2^32, two arrays that overlap.  n > max_batch is A1MPC_ERR_BATCH_TOO_LARGE.
+ * n == 0 is A1MPC_OK and launches nothing.  Host pointers (staged like the other caller-side entries), or (_device) device pointers, asynchronous on hip_stream
+ * (NULL = the handle's) and ordered like every other _device entry.
+ */
+typedef struct a1mpc_noise_config {
+    uint64_t seed;
+    double gyro_sigma, acc_sigma;            /* rad/s, m/s^2: white, per sample */
+    double gyro_bias_walk, acc_bias_walk;    /* std of the bias increment per call */
+    double att_sigma;                        /* rad: a small body-frame rotation on the quaternion */
+    double joint_pos_sigma, joint_vel_sigma; /* rad, rad/s */
+    double foot_force_sigma;                 /* N */
+} a1mpc_noise_config;
+void a1mpc_default_noise_config(a1mpc_noise_config* cfg);   /* seed 0, every sigma 0: off */
+a1mpc_status a1mpc_sensor_noise_batch(a1mpc_handle h, const a1mpc_noise_config* cfg, int32_t n, uint64_t robot0, uint64_t tick, double* quat, double* imu_acc_raw,
+                                      double* imu_gyro_raw, double* joint_pos, double* joint_vel, double* foot_force, double* imu_bias, double* z_out);
+a1mpc_status a1mpc_sensor_noise_batch_device(a1mpc_handle h, const a1mpc_noise_config* cfg, int32_t n, uint64_t robot0, uint64_t tick, double* d_quat,
+                                             double* d_imu_acc_raw, double* d_imu_gyro_raw, double* d_joint_pos, double* d_joint_vel, double* d_foot_force,
+                                             double* d_imu_bias, double* d_z_out, void* hip_stream);
 
 /*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
