@@ -1733,6 +1733,226 @@ thread_local std::string g_last_error;
 std::mutex g_cache_mu;
 thread_local bool g_clk_ran = false;
 thread_local bool g_gen_prefer_one_wave = false;
+
+// ---- episode record and batch summary (a1mpc_episode_update_batch, a1mpc_episode_summary_batch): what happened to each robot of a closed loop, kept on the device.  A
+// record is 16 doubles per robot, owned by the caller, all zero at the start of an episode: ticks, end_tick_p1, end_code, vel_err_sum, height_err_sum, tilt_max,
+// est_pos_err_sum, est_vel_err_sum, est_vel_err_max, effort_sum, fz_max, solver_bad, reach_bad, x0, y0, dist2 (the rules: include/a1mpc.h, restated elementwise in
+// tests/episode_ref.py).  The section sits behind the span the host emulations of the plant family compile; it uses that span's WaveStage, pl_legs and pl_pick.
+//   update    the plant kernels' layout: 16 robots per one-wave workgroup, lane = 4 robot + leg, every load issued up front, a robot's rows (state, R, the estimate, the
+//             commands, its plane, its record) through wave-private LDS; a lane loads its own leg's force, contact and reach byte.  Every lane of a robot computes the
+//             robot's whole new record (the leg sums are pl_legs, (leg 0 + leg 1) + (leg 2 + leg 3)), lane l parks words 4 l .. 4 l + 3 in the LDS image and the image
+//             leaves with 64 consecutive doubles per instruction.  Selects, no branches on data; IEEE + - * and comparisons only, no contraction
+//   reduce    one lane per row, 64 consecutive rows per one-wave workgroup, the rows through an LDS tile; a row becomes the 20 words of a summary (of itself), the xor
+//             butterfly 1, 2, 4 .. 32 combines them and lane 0 writes one partial summary.  The same kernel then reduces the partials, level by level, each level a
+//             launch: no atomics, nothing waits on another workgroup.  A sum is the balanced tree over the column padded with +0; dead lanes carry +0 in the sums and a
+//             copy of the wave's first row in the maxima, which changes neither
+constexpr int kEpWords = 16, kEpSummary = 20;
+struct EpisodeArgs {
+    int32_t n, stride;
+    double min_up, min_height;
+    double tick_p1;              // tick + 1, exact
+    const double *state, *R;
+    const double *est_pos, *est_vel;   // both or neither
+    const double *cmd, *pos_d_z, *ground;   // each may be null
+    const double* grf;           // with contacts, or both null
+    const uint8_t *contacts, *reach;
+    const int32_t* status;
+    double* episode;
+};
+__device__ __forceinline__ bool ep_finite(double x) { return x - x == 0.0; }   // (an infinity or a NaN gives a NaN)
+__global__ __launch_bounds__(64) void a1mpc_episode_update_kernel(const EpisodeArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double elds[kPlState + kPlR + 16 * kEpWords + 4 * 48 + 16];
+    double* const S = elds; double* const RL = S + kPlState; double* const EP = RL + kPlR; double* const PL = EP + 16 * kEpWords; double* const VL = PL + 48;
+    double* const CL = VL + 48; double* const GL = CL + 48; double* const ZL = GL + 48;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, stride = a.stride;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    const bool with_est = a.est_pos != nullptr, with_cmd = a.cmd != nullptr, with_z = a.pos_d_z != nullptr, sloped = a.ground != nullptr, with_f = a.grf != nullptr;
+    // every load, then the LDS writes, as in the plant step; the three-word rows are 48 words at most: one load per lane each
+    const int cs = live * stride, cr = live * 9, cw = live * kEpWords, c3 = live * 3;
+    const int cp = with_est ? c3 : 0, cc = with_cmd ? c3 : 0, cg = sloped ? c3 : 0, cz = with_z ? live : 0;
+    const double *gs = a.state + first * stride, *gr = a.R + first * 9;
+    double* const gw = a.episode + first * kEpWords;
+    const double *gp = with_est ? a.est_pos + first * 3 : a.R, *gv = with_est ? a.est_vel + first * 3 : a.R, *gc = with_cmd ? a.cmd + first * 3 : a.R;
+    const double *gg = sloped ? a.ground + first * 3 : a.R, *gz = with_z ? a.pos_d_z + first : a.R;
+    double vs[6], vr[3], vw[4];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; vs[m] = gs[e < cs ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vr[m] = gr[e < cr ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { const int e = lane + 64 * m; vw[m] = gw[e < cw ? e : 0]; }
+    const double vp = gp[lane < cp ? lane : 0], vv = gv[lane < cp ? lane : 0], vc = gc[lane < cc ? lane : 0], vg = gg[lane < cg ? lane : 0], vz = gz[lane < cz ? lane : 0];
+    double f[3] = {0.0, 0.0, 0.0};
+    bool stance = false, unreached = false;
+    if (with_f) {
+        const double* fp = a.grf + b * 12 + 3 * l;
+        f[0] = fp[0]; f[1] = fp[1]; f[2] = fp[2];
+        stance = a.contacts[b * 4 + l] != 0;
+    }
+    if (a.reach) unreached = a.reach[b * 4 + l] != 0;
+    const bool solved = a.status ? a.status[b] == 1 : true;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; if (e < cs) S[e] = vs[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cr) RL[e] = vr[m]; }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { const int e = lane + 64 * m; if (e < cw) EP[e] = vw[m]; }
+    if (lane < cp) { PL[lane] = vp; VL[lane] = vv; }
+    if (lane < cc) CL[lane] = vc;
+    if (lane < cg) GL[lane] = vg;
+    if (lane < cz) ZL[lane] = vz;
+    WaveStage::sync();
+    double pos[3], v[3], R[9], w[kEpWords];
+    {
+        const double* x = S + q * stride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pos[k] = x[3 + k]; v[k] = x[9 + k]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = RL[q * 9 + k];
+#pragma unroll
+        for (int k = 0; k < kEpWords; ++k) w[k] = EP[q * kEpWords + k];
+    }
+    // 2: the non-finite test over what this robot's rules read (a swing leg's force is selected away, not tested)
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) fin = fin && ep_finite(pos[k]) && ep_finite(v[k]);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) fin = fin && ep_finite(R[k]);
+    double ep[3] = {0.0, 0.0, 0.0}, ev[3] = {0.0, 0.0, 0.0}, c0 = 0.0, c1 = 0.0, pdz = 0.0, hz = 0.0;
+    if (with_est) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { ep[k] = PL[q * 3 + k]; ev[k] = VL[q * 3 + k]; fin = fin && ep_finite(ep[k]) && ep_finite(ev[k]); }
+    }
+    if (with_cmd) { c0 = CL[q * 3]; c1 = CL[q * 3 + 1]; fin = fin && ep_finite(c0) && ep_finite(c1); }
+    if (with_z) { pdz = ZL[q]; fin = fin && ep_finite(pdz); }
+    if (sloped) {
+        const double z0 = GL[q * 3], sx = GL[q * 3 + 1], sy = GL[q * 3 + 2];
+        fin = fin && ep_finite(z0) && ep_finite(sx) && ep_finite(sy);
+        hz = (z0 + sx * pos[0]) + sy * pos[1];
+    }
+    if (with_f) {
+        const bool leg_ok = !stance || (ep_finite(f[0]) && ep_finite(f[1]) && ep_finite(f[2]));
+        const double bad_legs = pl_legs(leg_ok ? 0.0 : 1.0);   // (every lane shuffles: not behind the && below)
+        fin = fin && bad_legs == 0.0;
+    }
+    // 1, 3, 4: frozen, or ended by this update, or accumulated
+    const double height = pos[2] - hz;
+    const int code = !fin ? 1 : (R[8] < a.min_up ? 2 : (height < a.min_height ? 3 : 0));
+    const bool frozen = w[2] != 0.0, ends = !frozen && code != 0, acc = !frozen && code == 0;
+    double nw[kEpWords];
+#pragma unroll
+    for (int k = 0; k < kEpWords; ++k) nw[k] = w[k];
+    nw[1] = ends ? a.tick_p1 : w[1];
+    nw[2] = ends ? static_cast<double>(code) : w[2];
+    // 5: every word whose inputs are given
+    nw[0] = acc ? w[0] + 1.0 : w[0];
+    if (with_cmd) {
+        const double ex = ((R[0] * v[0] + R[3] * v[1]) + R[6] * v[2]) - c0, ey = ((R[1] * v[0] + R[4] * v[1]) + R[7] * v[2]) - c1;
+        nw[3] = acc ? w[3] + (ex * ex + ey * ey) : w[3];
+    }
+    if (with_z) { const double ez = height - pdz; nw[4] = acc ? w[4] + ez * ez : w[4]; }
+    { const double t = 1.0 - R[8]; nw[5] = acc ? (t > w[5] ? t : w[5]) : w[5]; }
+    if (with_est) {
+        const double dx = ep[0] - pos[0], dy = ep[1] - pos[1], dz = ep[2] - pos[2], ux = ev[0] - v[0], uy = ev[1] - v[1], uz = ev[2] - v[2];
+        const double tp = (dx * dx + dy * dy) + dz * dz, tv = (ux * ux + uy * uy) + uz * uz;
+        nw[6] = acc ? w[6] + tp : w[6]; nw[7] = acc ? w[7] + tv : w[7]; nw[8] = acc ? (tv > w[8] ? tv : w[8]) : w[8];
+    }
+    if (with_f) {
+        const double sl = stance ? (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2] : 0.0;
+        const double effort = pl_legs(sl);
+        // the largest stance fz of the robot: a swing leg offers the record's own maximum, so the four-lane maximum is the rule's, leg by leg
+        double fz = stance ? (f[2] > w[10] ? f[2] : w[10]) : w[10];
+        { const double o = __shfl_xor(fz, 1, 64); fz = o > fz ? o : fz; }
+        { const double o = __shfl_xor(fz, 2, 64); fz = o > fz ? o : fz; }
+        nw[9] = acc ? w[9] + effort : w[9]; nw[10] = acc ? fz : w[10];
+    }
+    if (a.status) nw[11] = (acc && !solved) ? w[11] + 1.0 : w[11];
+    if (a.reach) { const double legs = pl_legs(unreached ? 1.0 : 0.0); nw[12] = acc ? w[12] + legs : w[12]; }
+    {
+        const bool opens = acc && w[0] == 0.0;
+        nw[13] = opens ? pos[0] : w[13]; nw[14] = opens ? pos[1] : w[14];
+        const double dx = pos[0] - nw[13], dy = pos[1] - nw[14];
+        nw[15] = acc ? dx * dx + dy * dy : w[15];
+    }
+    WaveStage::sync();   // (every lane has read its robot's record)
+    if (alive) {
+        double* o = EP + q * kEpWords + 4 * l;
+        o[0] = pl_pick(l, nw[0], nw[4], nw[8], nw[12]); o[1] = pl_pick(l, nw[1], nw[5], nw[9], nw[13]);
+        o[2] = pl_pick(l, nw[2], nw[6], nw[10], nw[14]); o[3] = pl_pick(l, nw[3], nw[7], nw[11], nw[15]);
+    }
+    WaveStage::sync();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { const int e = lane + 64 * m; if (e < cw) gw[e] = EP[e]; }
+}
+
+// n rows -> ceil(n / 64) partial summaries; rows are records (`records`) or partial summaries of the level below.  Words of a summary: 0 rows, 1 .. 4 rows with end_code
+// 0 / 1 / 2 / 3, 5 the smallest end_tick_p1 of an ended row (0: none; the last level writes it minus 1), 6 .. 8, 11, 12, 14, 16 .. 18 sums, 9 / 10 the largest tilt_max
+// and the lowest row that has it, 13, 15, 19 maxima
+struct EpisodeReduceArgs {
+    const double* in;
+    double* out;
+    int64_t rows;
+    int32_t records, last;
+};
+constexpr uint32_t kEpSums = 0x1F | (7u << 6) | (3u << 11) | (1u << 14) | (7u << 16), kEpMaxs = (1u << 13) | (1u << 15) | (1u << 19);
+__global__ __launch_bounds__(64) void a1mpc_episode_reduce_kernel(const EpisodeReduceArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double tile[64 * kEpSummary];
+    const int lane = static_cast<int>(threadIdx.x);
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 64;
+    if (first >= a.rows) return;   // (whole wave)
+    const int live = static_cast<int>(a.rows - first < 64 ? a.rows - first : 64);
+    const bool alive = lane < live, rec = a.records != 0;
+    const int width = rec ? kEpWords : kEpSummary, cnt = live * width;
+    const double* g = a.in + first * width;
+    double vt[kEpSummary];
+#pragma unroll
+    for (int m = 0; m < kEpSummary; ++m) { const int e = lane + 64 * m; vt[m] = g[e < cnt ? e : 0]; }
+    // a record row takes 17 words of the tile (64 x 17 <= 64 x 20): lanes that read their rows 16 words apart would all meet in two banks
+#pragma unroll
+    for (int m = 0; m < kEpSummary; ++m) { const int e = lane + 64 * m; if (e < cnt) tile[rec ? e + (e >> 4) : e] = vt[m]; }
+    WaveStage::sync();
+    const int src = alive ? lane : 0;   // (a dead lane: the wave's first row in the maxima, +0 in the sums)
+    const double* r = tile + src * (rec ? kEpWords + 1 : kEpSummary);
+    double v[kEpSummary];
+    if (rec) {
+        const double c = r[2];
+        v[0] = 1.0; v[1] = c == 0.0 ? 1.0 : 0.0; v[2] = c == 1.0 ? 1.0 : 0.0; v[3] = c == 2.0 ? 1.0 : 0.0; v[4] = c == 3.0 ? 1.0 : 0.0;
+        v[5] = c != 0.0 ? r[1] : 0.0;
+        v[6] = r[0]; v[7] = r[3]; v[8] = r[4]; v[9] = r[5]; v[10] = static_cast<double>(first + src); v[11] = r[6]; v[12] = r[7]; v[13] = r[8]; v[14] = r[9]; v[15] = r[10];
+        v[16] = r[11]; v[17] = r[12]; v[18] = r[15]; v[19] = r[15];
+    } else {
+#pragma unroll
+        for (int k = 0; k < kEpSummary; ++k) v[k] = r[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kEpSummary; ++k)
+        if (((kEpSums >> k) & 1u) || k == 5) v[k] = alive ? v[k] : 0.0;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const double om = __shfl_xor(v[9], s, 64), orow = __shfl_xor(v[10], s, 64), oe = __shfl_xor(v[5], s, 64);
+#pragma unroll
+        for (int k = 0; k < kEpSummary; ++k) {
+            if ((kEpSums >> k) & 1u) v[k] = v[k] + __shfl_xor(v[k], s, 64);
+            else if ((kEpMaxs >> k) & 1u) { const double o = __shfl_xor(v[k], s, 64); v[k] = o > v[k] ? o : v[k]; }
+        }
+        const bool take = om > v[9] || (om == v[9] && orow < v[10]);
+        v[9] = take ? om : v[9]; v[10] = take ? orow : v[10];
+        v[5] = v[5] == 0.0 ? oe : (oe == 0.0 ? v[5] : (oe < v[5] ? oe : v[5]));
+    }
+    if (lane == 0) {
+        double* o = a.out + static_cast<int64_t>(blockIdx.x) * kEpSummary;
+#pragma unroll
+        for (int k = 0; k < kEpSummary; ++k) o[k] = k == 5 && a.last ? v[5] - 1.0 : v[k];
+    }
+}
+
 // ---- the launch layer's table (a1mpc_common.hpp): (kernel, device) -> resident workgroups.  An entry exists once the kernel's dynamic-LDS limit is set on that device
 // and holds 0 until its occupancy has been asked for.  One mutex: handles of different threads may launch at the same time
 static std::mutex g_kernel_mu;
@@ -1991,6 +2211,7 @@ struct a1mpc_handle_s {
     // staging of the host-pointer entries of the caller-side stages, allocated on first use (ensure_aux; handed out by Staging)
     double *d_aux_in = nullptr, *d_aux_out = nullptr;
     uint8_t* d_aux_u8 = nullptr;
+    double* d_episode_ws = nullptr;   // a1mpc_episode_summary_batch: 20 doubles for the host entry's summary, then the partial summaries of every level (episode_ws_doubles)
     int32_t hint_n = 0;  // batch size the order was built for (0 = none)
     bool profiling = false;        // a1mpc_set_profiling: split-pipeline solves run the clock-stamped instantiation of the ADMM kernel
     long long* d_clk = nullptr;    // n x kTickStages cycles per QP (allocated on first use)
@@ -3592,7 +3813,7 @@ void a1mpc_destroy(a1mpc_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_tab, h->d_tab1, h->d_x0, h->d_xref, h->d_R, h->d_foot, h->d_aux, h->d_Rz, h->d_contact, h->d_grf,
-                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x, h->d_bal_acc, h->d_sensor_filt, h->d_sensor_cursor};
+                    h->d_u, h->d_iters, h->d_status, h->d_nfact, h->d_wx, h->d_wy, h->d_rho, h->d_prep, h->d_counter, h->d_in, h->d_out, h->d_order, h->d_cost, h->d_ct_state, h->d_ekf_state, h->d_aux_in, h->d_aux_out, h->d_aux_u8, h->d_episode_ws, h->d_foot_steps, h->d_contact_steps, h->d_prep_gen, h->d_carry, h->d_clk, h->d_tickrec, h->d_pv_sched, h->d_pv_foot, h->d_hs_u, h->d_hs_x, h->d_bal_acc, h->d_sensor_filt, h->d_sensor_cursor};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -3607,6 +3828,12 @@ void a1mpc_destroy(a1mpc_handle h) {
     delete h;
 }
 
+// what a1mpc_episode_summary_batch keeps on the device for max_batch rows: its host entry's 20 words, then one partial summary per 64 rows of every level but the last
+static size_t episode_ws_doubles(int32_t max_batch) {
+    size_t total = kEpSummary;
+    for (size_t m = (static_cast<size_t>(max_batch) + 63) / 64; m > 1; m = (m + 63) / 64) total += m * kEpSummary;
+    return total;
+}
 // The small-batch path of the host-pointer entries (pin_inputs): batches of up to A1MPC_ZERO_COPY_MAX QPs (default 8; 0 = always stage through device memory).
 // The general path takes it for at most 64 QPs, so that a large setting cannot inflate the pinned block a1mpc_create sizes for it.
 static int zero_copy_max() {
@@ -3692,6 +3919,8 @@ a1mpc_status a1mpc_create(const a1mpc_config* cfg, int32_t max_batch, int32_t de
     A1_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_out), out_max));
     A1_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_pin), h->h_pin_bytes, hipHostMallocDefault));
     { void* dp = nullptr; if (hipHostGetDevicePointer(&dp, h->h_pin, 0) == hipSuccess) h->d_pin = static_cast<char*>(dp); else (void)hipGetLastError(); }
+    // the episode summary's partials (a few bytes per robot): here, so that the first summary of a run allocates nothing; a failure is left to that call to report
+    if (hipMalloc(reinterpret_cast<void**>(&h->d_episode_ws), episode_ws_doubles(max_batch) * sizeof(double)) != hipSuccess) { h->d_episode_ws = nullptr; (void)hipGetLastError(); }
     // One-time, per process: the first launches / copies through a fresh HIP runtime cost milliseconds (code-object load, pool set-up);
     // a 400 Hz loop should not pay that on its first tick (measured 5 ms -> 0.4 ms), so the tick's operation mix is exercised here.
     static std::vector<int> runtime_warmed;   // the devices done: a sharded handle (a1mpc_sharded_*) creates one engine handle on every GPU of the node
@@ -4762,6 +4991,127 @@ a1mpc_status a1mpc_sensor_noise_batch(a1mpc_handle h, const a1mpc_noise_config* 
     double *d_bias = io(imu_bias, 6), *d_z = sg.out(z_out, kNoiseZ);
     A1_STAGED(sg);
     A1_STAGE_LAUNCH(launch_sensor_noise(*cfg, n, robot0, tick, d_quat, d_acc, d_gyro, d_jp, d_jv, d_ff, d_bias, d_z, s));
+    return sg.finish();
+}
+// ---- episode record and batch summary behind the C ABI: a1mpc_episode_update_kernel and a1mpc_episode_reduce_kernel; the records are the caller's, the handle holds the
+// summary's partials alone
+void a1mpc_default_episode_config(a1mpc_episode_config* c) {
+    if (!c) return;
+    c->min_up = 0.5; c->min_height = 0.12;
+}
+constexpr uint64_t kEpisodeTickEnd = (uint64_t{1} << 53) - 1;   // tick + 1 stays an exact double below it
+struct EpisodeIn {   // the inputs of an update beside state and R_world, in the entries' order
+    const double *root_pos, *root_lin_vel, *root_lin_vel_d, *root_pos_d_z, *ground, *grf_body;
+    const uint8_t* contacts;
+    const int32_t* status;
+    const uint8_t* reach;
+};
+// what the two update entries refuse, or null (all before the first HIP call; n > max_batch is A1_STAGE_DEVICE's)
+static const char* invalid_episode_update(a1mpc_handle h, const a1mpc_episode_config* cfg, int32_t n, uint64_t tick, const double* state, int32_t stride, const double* R_world,
+                                          const EpisodeIn& in, const double* episode) {
+    if (!h) return "null handle";
+    if (!cfg) return "null a1mpc_episode_config";
+    if (!state || !R_world) return "null state or R_world";
+    if (!episode) return "null episode";
+    if (stride != 12 && stride != 13 && stride != 22) return "state_stride must be 12, 13 or 22";
+    if (n < 0) return "negative n";
+    if (!std::isfinite(cfg->min_up) || cfg->min_up < -1.0 || cfg->min_up > 1.0) return "a1mpc_episode_config.min_up must be in [-1, 1]";
+    if (!std::isfinite(cfg->min_height)) return "a1mpc_episode_config.min_height must be finite";
+    if (tick >= kEpisodeTickEnd) return "tick must be below 2^53 - 1";
+    if ((in.root_pos == nullptr) != (in.root_lin_vel == nullptr)) return "root_pos and root_lin_vel are given together or not at all";
+    if ((in.grf_body == nullptr) != (in.contacts == nullptr)) return "grf_body and contacts are given together or not at all";
+    const struct { const void* p; size_t bytes; } ins[11] = {
+        {state, static_cast<size_t>(stride) * sizeof(double)}, {R_world, 9 * sizeof(double)}, {in.root_pos, 3 * sizeof(double)}, {in.root_lin_vel, 3 * sizeof(double)},
+        {in.root_lin_vel_d, 3 * sizeof(double)}, {in.root_pos_d_z, sizeof(double)}, {in.ground, 3 * sizeof(double)}, {in.grf_body, 12 * sizeof(double)}, {in.contacts, 4},
+        {in.status, sizeof(int32_t)}, {in.reach, 4}};
+    const uintptr_t pe = reinterpret_cast<uintptr_t>(episode), be = static_cast<uintptr_t>(n) * kEpWords * sizeof(double);
+    for (const auto& x : ins) {
+        if (!x.p) continue;
+        const uintptr_t pi = reinterpret_cast<uintptr_t>(x.p), bi = static_cast<uintptr_t>(n) * x.bytes;
+        if (pi < pe + be && pe < pi + bi) return "episode overlaps an input";
+    }
+    return nullptr;
+}
+static void launch_episode_update(const a1mpc_episode_config& cfg, int32_t n, uint64_t tick, const double* state, int32_t stride, const double* R_world, const EpisodeIn& in,
+                                  double* episode, hipStream_t s) {
+    EpisodeArgs a;
+    a.n = n; a.stride = stride; a.min_up = cfg.min_up; a.min_height = cfg.min_height; a.tick_p1 = static_cast<double>(tick + 1);
+    a.state = state; a.R = R_world; a.est_pos = in.root_pos; a.est_vel = in.root_lin_vel; a.cmd = in.root_lin_vel_d; a.pos_d_z = in.root_pos_d_z; a.ground = in.ground;
+    a.grf = in.grf_body; a.contacts = in.contacts; a.reach = in.reach; a.status = in.status; a.episode = episode;
+    hipLaunchKernelGGL(a1mpc_episode_update_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, a);
+}
+a1mpc_status a1mpc_episode_update_batch_device(a1mpc_handle h, const a1mpc_episode_config* cfg, int32_t n, uint64_t tick, const double* d_state, int32_t state_stride,
+                                               const double* d_R_world, const double* d_root_pos, const double* d_root_lin_vel, const double* d_root_lin_vel_d,
+                                               const double* d_root_pos_d_z, const double* d_ground, const double* d_grf_body, const uint8_t* d_contacts,
+                                               const int32_t* d_status, const uint8_t* d_reach, double* d_episode, void* hip_stream) {
+    const EpisodeIn in{d_root_pos, d_root_lin_vel, d_root_lin_vel_d, d_root_pos_d_z, d_ground, d_grf_body, d_contacts, d_status, d_reach};
+    if (const char* bad = invalid_episode_update(h, cfg, n, tick, d_state, state_stride, d_R_world, in, d_episode)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_episode_update(*cfg, n, tick, d_state, state_stride, d_R_world, in, d_episode, s));
+    return A1MPC_OK;
+}
+// the host-pointer entry: the inputs given are staged in, the records in and back (status: four bytes per robot of the byte staging, whose slices start 8-byte aligned)
+a1mpc_status a1mpc_episode_update_batch(a1mpc_handle h, const a1mpc_episode_config* cfg, int32_t n, uint64_t tick, const double* state, int32_t state_stride,
+                                        const double* R_world, const double* root_pos, const double* root_lin_vel, const double* root_lin_vel_d, const double* root_pos_d_z,
+                                        const double* ground, const double* grf_body, const uint8_t* contacts, const int32_t* status, const uint8_t* reach, double* episode) {
+    const EpisodeIn in{root_pos, root_lin_vel, root_lin_vel_d, root_pos_d_z, ground, grf_body, contacts, status, reach};
+    if (const char* bad = invalid_episode_update(h, cfg, n, tick, state, state_stride, R_world, in, episode)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const auto opt = [&sg](const double* host, size_t w) -> const double* { return host ? sg.in(host, w) : nullptr; };
+    const auto opt8 = [&sg](const uint8_t* host, size_t w) -> const uint8_t* { return host ? sg.in(host, w) : nullptr; };
+    const double *d_state = sg.in(state, static_cast<size_t>(state_stride)), *d_R = sg.in(R_world, 9);
+    EpisodeIn d;
+    d.root_pos = opt(root_pos, 3); d.root_lin_vel = opt(root_lin_vel, 3); d.root_lin_vel_d = opt(root_lin_vel_d, 3); d.root_pos_d_z = opt(root_pos_d_z, 1);
+    d.ground = opt(ground, 3); d.grf_body = opt(grf_body, 12); d.contacts = opt8(contacts, 4); d.reach = opt8(reach, 4);
+    d.status = reinterpret_cast<const int32_t*>(opt8(reinterpret_cast<const uint8_t*>(status), sizeof(int32_t)));
+    double* d_episode = sg.inout(episode, kEpWords);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_episode_update(*cfg, n, tick, d_state, state_stride, d_R, d, d_episode, s));
+    return sg.finish();
+}
+static const char* invalid_episode_summary(a1mpc_handle h, int32_t n, const double* episode, const double* summary_out) {
+    if (!h) return "null handle";
+    if (!episode) return "null episode";
+    if (!summary_out) return "null summary_out";
+    if (n < 0) return "negative n";
+    const uintptr_t pe = reinterpret_cast<uintptr_t>(episode), be = static_cast<uintptr_t>(n) * kEpWords * sizeof(double), po = reinterpret_cast<uintptr_t>(summary_out);
+    if (po < pe + be && pe < po + kEpSummary * sizeof(double)) return "summary_out overlaps episode";
+    return nullptr;
+}
+static a1mpc_status ensure_episode_ws(a1mpc_handle h) {   // (a1mpc_create's allocation failed: once more, and this time the failure is the call's)
+    if (!h->d_episode_ws) A1_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_episode_ws), episode_ws_doubles(h->max_batch) * sizeof(double)));
+    return A1MPC_OK;
+}
+// the levels of the tree, 64 rows per workgroup: n records -> ceil(n / 64) partials -> ... -> the summary; 1, 2 or 3 launches up to 64, 4096, 262 144 rows
+static void launch_episode_summary(a1mpc_handle h, int32_t n, const double* episode, double* summary_out, hipStream_t s) {
+    EpisodeReduceArgs a;
+    a.in = episode; a.rows = n; a.records = 1;
+    double* ws = h->d_episode_ws + kEpSummary;
+    for (;;) {
+        const int64_t groups = (a.rows + 63) / 64;
+        a.last = groups == 1; a.out = a.last ? summary_out : ws;
+        hipLaunchKernelGGL(a1mpc_episode_reduce_kernel, dim3(static_cast<unsigned>(groups)), dim3(64), 0, s, a);
+        if (a.last) return;
+        a.in = ws; a.rows = groups; a.records = 0; ws += groups * kEpSummary;
+    }
+}
+a1mpc_status a1mpc_episode_summary_batch_device(a1mpc_handle h, int32_t n, const double* d_episode, double* d_summary_out, void* hip_stream) {
+    if (const char* bad = invalid_episode_summary(h, n, d_episode, d_summary_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    if (a1mpc_status st = ensure_episode_ws(h); st != A1MPC_OK) return st;
+    A1_STAGE_LAUNCH(launch_episode_summary(h, n, d_episode, d_summary_out, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_episode_summary_batch(a1mpc_handle h, int32_t n, const double* episode, double* summary_out) {
+    if (const char* bad = invalid_episode_summary(h, n, episode, summary_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    if (a1mpc_status st = ensure_episode_ws(h); st != A1MPC_OK) return st;
+    Staging sg(h, n, s);
+    const double* d_episode = sg.in(episode, kEpWords);
+    A1_STAGED(sg);
+    A1_STAGE_LAUNCH(launch_episode_summary(h, n, d_episode, h->d_episode_ws, s));
+    A1_HIP(hipMemcpyAsync(summary_out, h->d_episode_ws, kEpSummary * sizeof(double), hipMemcpyDeviceToHost, s));
     return sg.finish();
 }
 #undef A1_STAGE_BEGIN

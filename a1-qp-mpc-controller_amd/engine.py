@@ -79,6 +79,18 @@ class NoiseConfig(C.Structure):  # a1mpc_noise_config: the generator's seed and 
                 ("att_sigma", C.c_double), ("joint_pos_sigma", C.c_double), ("joint_vel_sigma", C.c_double), ("foot_force_sigma", C.c_double)]
 
 
+class EpisodeConfig(C.Structure):  # a1mpc_episode_config: when an episode ends -- R22 below min_up (tilt), the body less than min_height above its ground
+    _fields_ = [("min_up", C.c_double), ("min_height", C.c_double)]
+
+
+EPISODE_WORDS = 16   # doubles per robot of an episode record; all zero is the start of an episode
+EPISODE_FIELDS = ("ticks", "end_tick_p1", "end_code", "vel_err_sum", "height_err_sum", "tilt_max", "est_pos_err_sum", "est_vel_err_sum", "est_vel_err_max", "effort_sum",
+                  "fz_max", "solver_bad", "reach_bad", "x0", "y0", "dist2")
+SUMMARY_FIELDS = ("n", "alive", "ended_nonfinite", "ended_tilt", "ended_height", "first_end_tick", "ticks", "vel_err_sum", "height_err_sum", "tilt_max", "tilt_max_row",
+                  "est_pos_err_sum", "est_vel_err_sum", "est_vel_err_max", "effort_sum", "fz_max", "solver_bad", "reach_bad", "dist2_sum", "dist2_max")
+# the optional inputs of a1mpc_episode_update_batch behind state and R_world, in its order: (name, columns (0: one value per robot), dtype)
+EPISODE_INPUTS = (("root_pos", 3, np.float64), ("root_lin_vel", 3, np.float64), ("root_lin_vel_d", 3, np.float64), ("root_pos_d_z", 0, np.float64), ("ground", 3, np.float64),
+                  ("grf_body", 12, np.float64), ("contacts", 4, np.uint8), ("status", 0, np.int32), ("reach", 4, np.uint8))
 NOISE_SENSORS = ("quat", "imu_acc_raw", "imu_gyro_raw", "joint_pos", "joint_vel", "foot_force")   # the arrays a1mpc_sensor_noise_batch works on in place, in its order
 NOISE_WIDTHS = dict(quat=4, imu_acc_raw=3, imu_gyro_raw=3, joint_pos=12, joint_vel=12, foot_force=4, imu_bias=6, z=44)
 TICK_SENSOR_POINTERS = ("quat", "imu_acc_raw", "imu_gyro_raw", "cmd", "mode_toggle", "body_height", "ctrl_state", "root_pos_d", "kp_linear_xy", "mpc_init_counter")
@@ -100,7 +112,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_noise_config", "a1mpc_sensor_noise_batch", "a1mpc_sensor_noise_batch_device",
+EXPORTS = ["a1mpc_default_episode_config", "a1mpc_episode_update_batch", "a1mpc_episode_update_batch_device", "a1mpc_episode_summary_batch",
+           "a1mpc_episode_summary_batch_device", "a1mpc_default_noise_config", "a1mpc_sensor_noise_batch", "a1mpc_sensor_noise_batch_device",
            "a1mpc_ground_step_batch", "a1mpc_ground_step_batch_device", "a1mpc_touch_sensors_batch", "a1mpc_touch_sensors_batch_device",
            "a1mpc_default_walk_config", "a1mpc_walk_step_batch", "a1mpc_walk_step_batch_device", "a1mpc_walk_sensors_batch", "a1mpc_walk_sensors_batch_device",
            "a1mpc_sensor_synthesis_batch", "a1mpc_sensor_synthesis_batch_device", "a1mpc_default_plant_config", "a1mpc_plant_step_batch", "a1mpc_plant_step_batch_device",
@@ -257,6 +270,15 @@ def load_library(path=None):
         lib.a1mpc_default_noise_config.argtypes = [C.POINTER(NoiseConfig)]; lib.a1mpc_default_noise_config.restype = None
         lib.a1mpc_sensor_noise_batch.argtypes = [vp, C.POINTER(NoiseConfig), i32, u64, u64] + [dp] * 8; lib.a1mpc_sensor_noise_batch.restype = C.c_int
         lib.a1mpc_sensor_noise_batch_device.argtypes = [vp, C.POINTER(NoiseConfig), i32, u64, u64] + [vpp] * 8 + [vpp]; lib.a1mpc_sensor_noise_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_episode_update_batch"):   # (episode record and batch summary; an older build bound by hand for an A/B lacks them)
+        u64 = C.c_uint64; u8p = C.POINTER(C.c_uint8); i32p = C.POINTER(C.c_int32)
+        lib.a1mpc_default_episode_config.argtypes = [C.POINTER(EpisodeConfig)]; lib.a1mpc_default_episode_config.restype = None
+        lib.a1mpc_episode_update_batch.argtypes = [vp, C.POINTER(EpisodeConfig), i32, u64, dp, i32] + [dp] * 7 + [u8p, i32p, u8p, dp]
+        lib.a1mpc_episode_update_batch.restype = C.c_int
+        lib.a1mpc_episode_update_batch_device.argtypes = [vp, C.POINTER(EpisodeConfig), i32, u64, vpp, i32] + [vpp] * 11 + [vpp]
+        lib.a1mpc_episode_update_batch_device.restype = C.c_int
+        lib.a1mpc_episode_summary_batch.argtypes = [vp, i32, dp, dp]; lib.a1mpc_episode_summary_batch.restype = C.c_int
+        lib.a1mpc_episode_summary_batch_device.argtypes = [vp, i32, vpp, vpp, vpp]; lib.a1mpc_episode_summary_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -771,6 +793,65 @@ class Engine:
                                                       _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_imu_bias), _dev(d_z),
                                                       C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_sensor_noise_batch_device")
+
+    # ---- episode record and batch summary: what happened to each robot of a closed loop, kept on the device and read with one small copy at the end ----
+    def episode_config(self, **fields):
+        """a1mpc_default_episode_config (min_up 0.5, min_height 0.12) with `fields` overridden"""
+        ec = EpisodeConfig(); self.lib.a1mpc_default_episode_config(C.byref(ec))
+        for k, v in fields.items():
+            if not hasattr(ec, k):
+                raise KeyError(k)
+            setattr(ec, k, float(v))
+        return ec
+
+    def episode_update(self, episode, tick, state, R_world, root_pos=None, root_lin_vel=None, root_lin_vel_d=None, root_pos_d_z=None, ground=None, grf_body=None, contacts=None,
+                       status=None, reach=None, config=None):
+        """a1mpc_episode_update_batch: `episode` (n, 16), a writeable C-contiguous float64 array, is updated IN PLACE with this tick's truth (state (n, 12 / 13 / 22),
+        R_world (n, 9)) and whichever of the optional inputs are given (EPISODE_INPUTS) -> episode"""
+        if not (isinstance(episode, np.ndarray) and episode.dtype == np.float64 and episode.flags.c_contiguous and episode.flags.writeable and episode.ndim == 2
+                and episode.shape[1] == EPISODE_WORDS):
+            raise ValueError(f"episode must be a writeable C-contiguous float64 array of shape (n, {EPISODE_WORDS}): it is changed in place")
+        n = episode.shape[0]
+        state = np.ascontiguousarray(state, dtype=np.float64); R_world = np.ascontiguousarray(R_world, dtype=np.float64).reshape(n, 9)
+        if state.shape[0] != n:
+            raise ValueError("state must have one row per record")
+        given = dict(root_pos=root_pos, root_lin_vel=root_lin_vel, root_lin_vel_d=root_lin_vel_d, root_pos_d_z=root_pos_d_z, ground=ground, grf_body=grf_body,
+                     contacts=contacts, status=status, reach=reach)
+        args = []
+        for k, cols, dt in EPISODE_INPUTS:
+            v = given[k]
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=dt).reshape((n, cols) if cols else (n,))
+            given[k] = v   # (kept alive over the call)
+            args.append(None if v is None else v.ctypes.data_as(C.POINTER({np.float64: C.c_double, np.uint8: C.c_uint8, np.int32: C.c_int32}[dt])))
+        ec = config if config is not None else self.episode_config()
+        rc = self.lib.a1mpc_episode_update_batch(self._h, C.byref(ec), n, int(tick), _dp(state), int(state.shape[1]), _dp(R_world), *args, _dp(episode))
+        _check(self.lib, rc, "a1mpc_episode_update_batch")
+        return episode
+
+    def episode_update_device(self, n, tick, d_episode, d_state, state_stride, d_R_world, d_root_pos=None, d_root_lin_vel=None, d_root_lin_vel_d=None, d_root_pos_d_z=None,
+                              d_ground=None, d_grf_body=None, d_contacts=None, d_status=None, d_reach=None, config=None, stream=None):
+        """device pointers (torch tensors), asynchronous on `stream`: behind the plant step of a tick on the loop's stream it folds that tick into the n records of
+        d_episode (n x 16 float64, zeroed at the start of an episode); tick is passed by value"""
+        ec = config if config is not None else self.episode_config()
+        rc = self.lib.a1mpc_episode_update_batch_device(self._h, C.byref(ec), int(n), int(tick), _dev(d_state), int(state_stride), _dev(d_R_world), _dev(d_root_pos),
+                                                        _dev(d_root_lin_vel), _dev(d_root_lin_vel_d), _dev(d_root_pos_d_z), _dev(d_ground), _dev(d_grf_body), _dev(d_contacts),
+                                                        _dev(d_status), _dev(d_reach), _dev(d_episode), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_episode_update_batch_device")
+
+    def episode_summary(self, episode):
+        """a1mpc_episode_summary_batch: n records (n, 16) -> the 20 words of SUMMARY_FIELDS"""
+        episode = np.ascontiguousarray(episode, dtype=np.float64)
+        if episode.ndim != 2 or episode.shape[1] != EPISODE_WORDS:
+            raise ValueError(f"episode must have shape (n, {EPISODE_WORDS})")
+        out = np.zeros(len(SUMMARY_FIELDS))
+        _check(self.lib, self.lib.a1mpc_episode_summary_batch(self._h, episode.shape[0], _dp(episode), _dp(out)), "a1mpc_episode_summary_batch")
+        return out
+
+    def episode_summary_device(self, n, d_episode, d_summary, stream=None):
+        """device pointers, asynchronous on `stream`: d_summary (20 float64) receives the summary of the n records of d_episode"""
+        rc = self.lib.a1mpc_episode_summary_batch_device(self._h, int(n), _dev(d_episode), _dev(d_summary), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_episode_summary_batch_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

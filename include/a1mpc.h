@@ -956,6 +956,73 @@ a1mpc_status a1mpc_sensor_noise_batch_device(a1mpc_handle h, const a1mpc_noise_c
                                              double* d_imu_bias, double* d_z_out, void* hip_stream);
 
 /*
+ * Episode record and batch summary for closed-loop runs, on the device.  The loop  sensors -> noise -> control tick -> plant step  never leaves the GPU; this is its
+ * last stage: a1mpc_episode_update_batch_device, called once per tick behind the plant step on the loop's stream, keeps 16 doubles per robot -- whether it stayed up and
+ * until when, how well it tracked its command, how well the estimator tracked the plant -- and a1mpc_episode_summary_batch_device reduces n records to 20 numbers, so
+ * that a run of 65 536 robots is read with one small copy at its end.  Two kernels and a family of their own, a1mpc_episode_*: the entries above are unchanged.
+ *
+ * UPDATE.  in (all device pointers in the _device entry, host pointers staged like the other caller-side entries otherwise):
+ *        state, state_stride   n x 12 / 13 / 22, the plant's truth: pos = state[3:6) and v = state[9:12) are read
+ *        R_world               n x 9 row-major, the truth attitude
+ *        root_pos, root_lin_vel   n x 3 each, the tick's estimate (a1mpc_tick_buffers); optional, as a pair
+ *        root_lin_vel_d        n x 3, the body-frame command (x and y are read); optional
+ *        root_pos_d_z          n; optional
+ *        ground                n x 3, z0, sx, sy as in a1mpc_ground_step_batch; optional (NULL: the plane z = 0)
+ *        grf_body, contacts    n x 12 doubles, n x 4 bytes; optional, as a pair
+ *        status                n int32, the solver's; optional        reach   n x 4 bytes; optional
+ *        tick                  by value, below 2^53 - 1               cfg     min_up, min_height (a1mpc_default_episode_config: 0.5, 0.12)
+ * in / out  episode  n x 16 doubles, owned by the caller; the handle gets no state.  An all-zero record is the start of an episode: a memset is a reset.
+ *   word  0 ticks            updates accumulated            1 end_tick_p1   0 while alive, else tick + 1 of the update that ended the episode
+ *         2 end_code         0 alive, 1 non-finite input, 2 tilt, 3 height
+ *         3 vel_err_sum      += ex ex + ey ey;  vb_k = (R0k v0 + R1k v1) + R2k v2 (vb = R^T v),  e = vb - root_lin_vel_d
+ *         4 height_err_sum   += ez ez;  ez = (pos_z - hz) - root_pos_d_z,  hz = (z0 + sx pos_x) + sy pos_y, or +0 without ground
+ *         5 tilt_max         max of 1 - R22
+ *         6 est_pos_err_sum  += (dx dx + dy dy) + dz dz, d = root_pos - pos      7 est_vel_err_sum  the same on root_lin_vel - v      8 est_vel_err_max  max of 7's term
+ *         9 effort_sum       += (s0 + s1) + (s2 + s3);  s_l = (fx fx + fy fy) + fz fz on a stance leg, +0 selected on a swing leg
+ *        10 fz_max           max over stance legs of the body-frame fz           11 solver_bad  += 1 when status != 1       12 reach_bad  += legs with reach != 0
+ *        13, 14 x0, y0       pos_x, pos_y of the first accumulated update (the one that finds ticks == 0)
+ *        15 dist2            (pos_x - x0)^2 + (pos_y - y0)^2 of the latest accumulated update
+ * Per robot, in this order: (1) a record with end_code != 0 keeps every bit: it is frozen.  (2) If any value this robot's rules read is not finite -- pos, v, R, the
+ * estimate, the command's x and y, root_pos_d_z, its ground row, the forces of its STANCE legs (a swing leg's force is selected away and not tested, as in the plant)
+ * -- end_code = 1, end_tick_p1 = tick + 1, and nothing else changes.  (3) R22 < min_up ends with code 2.  (4) pos_z - hz < min_height ends with code 3.  (5) Otherwise
+ * every word whose inputs are given is accumulated; a word whose input is NULL keeps its bits.  A maximum is (x > m) ? x : m.  The update that ends an episode
+ * accumulates nothing.
+ * Arithmetic: IEEE + - * and comparisons only, contraction off, no fused multiply-add, sums in the order written.  A robot's record is a pure function of its own
+ * inputs: the same bits at every batch size, position in the batch and entry.
+ *
+ * SUMMARY.  summary_out, 20 doubles (device-resident in the _device entry):
+ *   word  0 n       1 .. 4 records with end_code 0 / 1 / 2 / 3       5 the smallest end_tick_p1 - 1 over ended records, -1 when none ended
+ *         6 sum of ticks   7 of vel_err_sum   8 of height_err_sum   9 max of tilt_max   10 the LOWEST row that attains word 9   11 sum of est_pos_err_sum
+ *        12 sum of est_vel_err_sum   13 max of est_vel_err_max   14 sum of effort_sum   15 max of fz_max   16 sum of solver_bad   17 of reach_bad   18 sum of dist2
+ *        19 max of dist2
+ * Every sum is over all n rows, frozen records included, and is DEFINED by a balanced tree: the column padded to the next power of two with +0, then x'[i] = x[2i] +
+ * x[2i + 1] until one value is left.  It does not depend on the launch geometry (every summed word of a record is at least +0, so the + (+0) of the radix-64 levels
+ * the kernel uses is exact).  No atomics: a1mpc_episode_reduce_kernel runs level by level, 64 rows per wavefront, the levels separated by launches on the stream; the
+ * partials live in a workspace sized from max_batch at a1mpc_create.
+ * What it is not: no reset of the handle's state (EKF, contact filters) for a robot that fell -- a fallen robot's record freezes, its loop goes on; no quantiles or
+ * histograms; sums, not means (divide by word 6 or word 0 yourself); one batch, not merged across shards or handles.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch, every array left untouched: a null handle (first), cfg, state, R_world
+ * or episode; a stride other than 12 / 13 / 22; n < 0; min_up outside [-1, 1] or not finite; min_height not finite; tick >= 2^53 - 1; half of a pair (root_pos /
+ * root_lin_vel, grf_body / contacts); episode overlapping an input; for the summary a null handle, episode or summary_out, n < 0, summary_out overlapping episode.
+ * n > max_batch is A1MPC_ERR_BATCH_TOO_LARGE.  n == 0 is A1MPC_OK, launches nothing and writes nothing.  The _device entries are asynchronous on hip_stream (NULL = the
+ * handle's) and ordered like every other _device entry.
+ */
+typedef struct a1mpc_episode_config {
+    double min_up;      /* the episode ends (code 2) when R22 falls below it: 0.5 is a tilt of 60 degrees */
+    double min_height;  /* ... (code 3) when the body is less than this above its ground, m */
+} a1mpc_episode_config;
+void a1mpc_default_episode_config(a1mpc_episode_config* cfg);   /* 0.5, 0.12 */
+a1mpc_status a1mpc_episode_update_batch(a1mpc_handle h, const a1mpc_episode_config* cfg, int32_t n, uint64_t tick, const double* state, int32_t state_stride,
+                                        const double* R_world, const double* root_pos, const double* root_lin_vel, const double* root_lin_vel_d, const double* root_pos_d_z,
+                                        const double* ground, const double* grf_body, const uint8_t* contacts, const int32_t* status, const uint8_t* reach, double* episode);
+a1mpc_status a1mpc_episode_update_batch_device(a1mpc_handle h, const a1mpc_episode_config* cfg, int32_t n, uint64_t tick, const double* d_state, int32_t state_stride,
+                                               const double* d_R_world, const double* d_root_pos, const double* d_root_lin_vel, const double* d_root_lin_vel_d,
+                                               const double* d_root_pos_d_z, const double* d_ground, const double* d_grf_body, const uint8_t* d_contacts,
+                                               const int32_t* d_status, const uint8_t* d_reach, double* d_episode, void* hip_stream);
+a1mpc_status a1mpc_episode_summary_batch(a1mpc_handle h, int32_t n, const double* episode, double* summary_out);
+a1mpc_status a1mpc_episode_summary_batch_device(a1mpc_handle h, int32_t n, const double* d_episode, double* d_summary_out, void* hip_stream);
+
+/*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
  * (hessian, gradient, lb, ub: S/ConvexMpc.h:84-93, S/ConvexMpc.cpp:158-245) for n problems, formed on the GPU from the same inputs as
  * a1mpc_solve_batch_strided.  P_out n x (12H)^2 (row-major, symmetric), g_out n x 12H, l_out / u_out n x 20H (the constraint matrix is
