@@ -531,3 +531,150 @@ def plan_inputs(scen, rng, n, ps):
             vd[b, :2] = 0.0; vd[b, ax] = 3.0 * sg
     vd[8::9] = 0.0
     return dict(v=v, Rz=Rz, R=R, pos=pos, vd=vd)
+
+
+# ---- a generic set of robot constants (tests/test_generic_constants_host.py, tests/test_gpu_generic_constants.py) ----
+# Every scenarios.PARAM_SETS entry has a diagonal inertia_body, q[3] = q[4] = 0 and one r repeated over the lanes of a leg (most: over all twelve).  No caller has to keep
+# that structure and the kernels do not assume it: the set below has none of it.  inertia = Rr diag(0.0158533, 0.0377999, 0.0456542) Rr', symmetrised, Rr the Rodrigues
+# rotation of the vector (-0.2405794275760342, -0.39730769868844346, -0.07450848662857455) (numpy's default_rng(5).normal(0, 0.3, 3)), written out so that it does not
+# depend on a generator; r[k] = 1e-7 (1 + k / 4).  dt, mu and the force limits stay the scenario's.
+GENERIC_CONSTANTS = dict(
+    mass=11.3, q=[20.0, 10.0, 1.0, 3.0, 7.0, 420.0, 0.05, 0.07, 0.03, 30.0, 25.0, 10.0, 0.0],
+    r=[1e-07, 1.25e-07, 1.5e-07, 1.75e-07, 2e-07, 2.25e-07, 2.5e-07, 2.75e-07, 3e-07, 3.2499999999999996e-07, 3.5e-07, 3.75e-07],
+    inertia=[0.02033138319319339, -0.0002215375332723924, -0.010531835564711142, -0.0002215375332723924, 0.03826292733232652, 0.001943689135907053,
+             -0.010531835564711142, 0.001943689135907053, 0.040713089474480074])
+GENERIC_MOVE_N = 1e-3     # 100 x helpers.TOL_FORCE_N: what a variant below must move the yardstick's forces by, on at least half of a batch
+
+
+def generic_params(params, **par):
+    """a scenario's parameter dict with the generic constants in place of its mass, inertia, q and r (dt, mu, force limits and the nominal feet stay); par: overrides"""
+    out = dict(params, **{k: (list(v) if isinstance(v, list) else v) for k, v in GENERIC_CONSTANTS.items()})
+    out.update(par)
+    return out
+
+
+def generic_scenario(scen, h, n, seed=None, **par):
+    """family_scenario with the generic constants; par: further robot constants (mu, fz_min, fz_max, or one of generic_variants())"""
+    return family_scenario(scen, h, n, generic_params({}, **par), seed=seed)
+
+
+def generic_variants():
+    """{name: constants that replace GENERIC_CONSTANTS' with ONE property put back to the structure of scenarios.PARAM_SETS, or two words exchanged}: what a kernel computes
+    that reads a wrong pair of inertia words, drops or swaps q[3] / q[4], indexes r by leg instead of by lane, or was handed the diagonal only"""
+    G = GENERIC_CONSTANTS
+    I = np.array(G["inertia"]).reshape(3, 3); q = np.array(G["q"]); r = np.array(G["r"])
+    swap = I.copy(); swap[0, 1], swap[0, 2] = I[0, 2], I[0, 1]; swap[1, 0], swap[2, 0] = I[2, 0], I[1, 0]
+    q67 = q.copy(); q67[[6, 7]] = q[[7, 6]]
+    q34 = q.copy(); q34[[3, 4]] = q[[4, 3]]
+    q00 = q.copy(); q00[[3, 4]] = 0.0
+    return {"off-diagonals zeroed": dict(inertia=np.diag(np.diag(I)).reshape(9).tolist()), "I01 <-> I02": dict(inertia=swap.reshape(9).tolist()),
+            "q[6] <-> q[7]": dict(q=q67.tolist()), "q[3] = q[4] = 0": dict(q=q00.tolist()), "q[3] <-> q[4]": dict(q=q34.tolist()),
+            "r uniform at its mean": dict(r=[float(r.mean())] * 12), "r rolled by one lane": dict(r=np.roll(r, 1).tolist())}
+
+
+def assert_variants_move(label, full, variants, move=GENERIC_MOVE_N, share=0.5):
+    """The sensitivity precondition of the generic-constants tests, on the YARDSTICK's forces (k, ...) of one batch: every variant must move them by more than `move`
+    (100 x TOL_FORCE_N) on at least `share` of the QPs -- or a pass of that batch could not tell the generic set from the structured one.  Prints the shares and medians;
+    -> {name: (share, median move)}"""
+    k = len(full); out = {}
+    for name, var in variants.items():
+        d = np.abs(np.asarray(var).reshape(k, -1) - np.asarray(full).reshape(k, -1)).max(axis=1)
+        out[name] = (float((d > move).mean()), float(np.median(d)))
+    print(f"{label}: share of {k} QPs whose yardstick forces move by more than {move:g} N (median move): " + ", ".join(f"{n} {s:.2f} ({m:.1e} N)" for n, (s, m) in out.items()))
+    weak = {n: v for n, v in out.items() if not v[0] >= share}
+    assert not weak, (label, weak)
+    return out
+
+
+def oracle_variant_forces(oracle, sc, idx, settings=None, foot=None, fs=0, contact=None, cs=0, **var):
+    """the oracle's full-horizon forces (len(idx), 12 h) of the QPs idx of a batch with the robot constants `var` replacing the batch's own"""
+    from helpers import oracle_params
+    v = dict(sc, params=dict(sc["params"], **var))
+    st = oracle.default_settings() if settings is None else settings
+    return oracle_strided(oracle, oracle_params(oracle, v), st, v, sc["foot"] if foot is None else foot, fs, sc["contact"] if contact is None else contact, cs, idx)["u"]
+
+
+def assert_batch_is_sensitive(label, oracle, sc, idx, ref_u, settings=None, **strided):
+    """assert_variants_move for the QPs idx of a batch whose yardstick forces at the full set are ref_u"""
+    return assert_variants_move(label, ref_u, {name: oracle_variant_forces(oracle, sc, idx, settings, **strided, **var) for name, var in generic_variants().items()})
+
+
+# the settings cases of the generic-constants tests: the defaults, three Ruiz passes, and the friction / force-limit set with fz_min > 0 (its first iteration touches r)
+GENERIC_FAST_CASES = [dict(), dict(scaling=3), dict(zip(PARAM_KEYS, FRICTION_CASES[1]))]
+
+
+def generic_case_id(case):
+    return case_id(case) or "default"
+
+
+def generic_strided(scen, h, n):
+    """_strided_inputs (per-step feet, a contact schedule) of n QPs at horizon h with the generic constants -> (sc, foot, foot_stride, contact, contact_stride)"""
+    sc, foot, fs, contact, cs = _strided_inputs(scen, np.random.default_rng(9400 + h + n), h, n, True, True)
+    sc["params"] = generic_params(sc["params"])
+    return sc, foot, fs, contact, cs
+
+
+def generic_warm_ticks(scen, h=10, n=64):
+    """the four ticks of test_warm_start_modes_with_non_default_settings' pattern on a generic batch (slowly moving states, every leg changing role at tick 2) -> a list of
+    four scenarios (the arrays of a tick are copies)"""
+    rng = np.random.default_rng(9300 + 7 * h + n)
+    sc = generic_scenario(scen, h, n, seed=9300 + h + n)
+    ticks = []
+    for t in range(4):
+        if t > 0:
+            sc["x0"][:, :12] += rng.normal(0, 2e-3, (n, 12)); sc["foot"] += rng.normal(0, 1e-3, (n, 12))
+        if t == 2:
+            sc["contact"][:] = 1 - sc["contact"]
+            sc["contact"][sc["contact"].sum(1) == 0] = [1, 0, 0, 1]
+        ticks.append({k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in sc.items()})
+    return ticks
+
+
+def oracle_warm_chain(oracle, x87, ticks, mode, h):
+    """every robot of generic_warm_ticks chained through the oracle (mode 1: x, y, rho carried; mode 2: the update path) -> per tick (ref dict(u, grf, iters, status),
+    x87_solve(j): the extended-precision solve of robot j's tick from the state the oracle's solve started from)"""
+    from helpers import oracle_params
+    n = len(ticks[0]["x0"])
+    pr = oracle_params(oracle, ticks[0]); st = oracle.default_settings(warm_start=1)
+    xpr = x87.params(ticks[0]["params"], h); xst = x87.settings(warm_start=1)
+    carries = [oracle.update_carry(h) for _ in range(n)]
+    wx = [np.zeros(12 * h) for _ in range(n)]; wy = [np.zeros(20 * h) for _ in range(n)]; rho = [None] * n
+    out = []
+    for sc in ticks:
+        before = [(carries[b].copy(), wx[b].copy(), wy[b].copy(), rho[b]) for b in range(n)]
+        ref = dict(u=np.zeros((n, 12 * h)), grf=np.zeros((n, 12)), iters=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        for b in range(n):
+            a = (sc["x0"][b], sc["xref"][b], sc["R"][b], sc["foot"][b], sc["contact"][b])
+            if mode == 2:
+                o = oracle.mpc_solve_update(pr, st, *a, carries[b])
+            else:
+                o = oracle.mpc_solve(pr, st, *a, warm_x=wx[b], warm_y=wy[b], warm_rho=rho[b])
+                wx[b], wy[b], rho[b] = o["warm_x"], o["warm_y"], o["rho"]
+            ref["u"][b], ref["grf"][b], ref["iters"][b], ref["status"][b] = o["u"], o["grf"], o["info"].iters, o["info"].status
+
+        def x87_solve(j, sc=sc, before=before):
+            c, x, y, r = before[j]
+            a = (sc["x0"][j], sc["xref"][j], sc["R"][j], sc["foot"][j], sc["contact"][j])
+            return x87.mpc_solve_update(xpr, xst, *a, c) if mode == 2 else x87.mpc_solve(xpr, xst, *a, warm_x=x, warm_y=y, warm_rho=r)
+        out.append((ref, x87_solve))
+    return out
+
+
+def yardstick_alone(label, ref, x87_solve, case, threads=16):
+    """The precondition of held_to_oracle's cap, on the yardstick ONLY: ref = the oracle's dict(u, grf, iters, status) of k QPs, x87_solve(j) its extended-precision
+    build on QP j.  Both stop at the same iteration on every QP, and the share of QPs further than TOL_FORCE_N apart is within the cap held_to_oracle grants `case`
+    (fewer than X87_PCT per cent; at most X87_PCT_NOISY on NOISY_CASES).  -> dict(above, worst)"""
+    from concurrent.futures import ThreadPoolExecutor
+    from helpers import TOL_FORCE_N
+    k = len(ref["iters"])
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        xs = list(pool.map(x87_solve, range(k)))
+    it_x = np.array([x["iters"] for x in xs])
+    d = np.array([max(np.abs(np.ravel(ref["u"][j]) - np.ravel(xs[j]["u"])).max(), np.abs(np.ravel(ref["grf"][j]) - np.ravel(xs[j]["grf"])).max()) for j in range(k)])
+    above = int((~(d <= TOL_FORCE_N)).sum())
+    allowed = (X87_PCT_NOISY * k) // 100 if case in NOISY_CASES else (X87_PCT * k - 1) // 100
+    print(f"{label} {generic_case_id(case)}: {k} QPs, same iteration as x87 on {int((it_x == ref['iters']).sum())}, worst oracle-vs-x87 {d.max():.2e} N, {above} above the bar "
+          f"({allowed} may be), statuses {dict(zip(*np.unique(ref['status'], return_counts=True)))}")
+    assert np.array_equal(it_x, ref["iters"]), (label, case, np.flatnonzero(it_x != ref["iters"])[:8])
+    assert above <= allowed, (label, case, above, allowed)
+    return dict(above=above, worst=float(d.max()))
