@@ -1985,6 +1985,108 @@ a1mpc_status resident_workgroups(int dev, const void* fn, int threads, size_t ld
     return A1MPC_OK;
 }
 
+// ---- respawn (a1mpc_respawn_reset_batch, a1mpc_respawn_batch, a1mpc_respawn_rows_device): a robot whose episode is over gets its lane back on the device.  Two
+// kernels in a section of their own, behind every span a host emulation of another family compiles; neither knows a struct of the handle: the launcher hands the first
+// a table of regions (where a robot's bytes of each state block lie), the second the caller's table of rows.  The rules: include/a1mpc.h, restated in
+// tests/respawn_ref.py; the text below is compiled for the host by tests/emu/respawn_host.py.
+//   both      one wavefront owns 64 consecutive robots: lane l decides robot l (its mask byte, or rules 1 - 3 on its record and life), one ballot gives the wave's set,
+//             and a wave-uniform loop takes the set's robots one by one with all 64 lanes on that robot's words: consecutive lanes, consecutive words.  A wave with an
+//             empty set has read one byte (the decision: 24) per robot and leaves.  Plain stores; no LDS, no atomics, nothing waits on another wavefront
+//   region    `runs` runs of `run_bytes` at `run_step` bytes from each other, `robot_stride` bytes between two robots.  A block that is contiguous per robot is one
+//             run (lane = word); a block that holds one word per slot and robot, [slot][max_batch], is `runs` runs of one word (lane = slot).  The launcher builds no
+//             other shape.  Words are 8 bytes unless run_bytes is an odd multiple of 4 (the IMU count / cursor)
+//   decision  copies, comparisons and integer arithmetic: no floating-point operation rounds
+constexpr int kRespawnRegions = 10, kRespawnWords = 16, kRespawnRowsMax = 16;
+struct RespawnRegion { char* base; int64_t robot_stride, run_step; int32_t run_bytes, runs; };
+struct RespawnArgs {
+    int32_t n, n_regions;
+    const uint8_t* mask;         // given (a1mpc_respawn_reset_batch): bit 0 selects, nothing below is read; or null: the rules
+    double* record;              // n x 16, in / out
+    int32_t* life;               // n x 2, in / out: hold, episodes_done
+    double* finished;            // n x 16 or null
+    uint8_t* mask_out;           // n
+    uint32_t codes;
+    int32_t hold_ticks;
+    double max_ticks;            // exact (below 2^53); 0: no limit
+    RespawnRegion region[kRespawnRegions];
+};
+__global__ __launch_bounds__(64) void a1mpc_respawn_kernel(const RespawnArgs a) {
+    const int lane = static_cast<int>(threadIdx.x);
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 64;
+    if (first >= a.n) return;   // (whole wave)
+    const int64_t b = first + lane;
+    const bool alive = b < a.n;
+    int m = 0;
+    if (a.mask) {
+        if (alive) m = a.mask[b] & 1;
+    } else if (alive) {
+        const int hold = a.life[2 * b], done = a.life[2 * b + 1];
+        const double ticks = a.record[b * kRespawnWords], code = a.record[b * kRespawnWords + 2];
+        const bool ended = (code == 1.0 && (a.codes & 2u)) || (code == 2.0 && (a.codes & 4u)) || (code == 3.0 && (a.codes & 8u));
+        const bool timed = code == 0.0 && a.max_ticks > 0.0 && ticks >= a.max_ticks;
+        m = hold > 0 ? 2 : (ended || timed ? 1 : 0);
+        a.mask_out[b] = static_cast<uint8_t>(m);
+        if (m == 2) a.life[2 * b] = hold - 1;
+        if (m == 1) { a.life[2 * b] = a.hold_ticks; a.life[2 * b + 1] = done + 1; }
+    }
+    const unsigned long long reset = __ballot(m == 1);
+    if (!a.mask) {   // the records of the respawned and the held: 16 lanes on a record
+        const unsigned long long cleared = __ballot(m != 0);
+        for (unsigned long long set = cleared; set != 0; set &= set - 1) {
+            const int r = __builtin_ctzll(set);
+            double* const rec = a.record + (first + r) * kRespawnWords;
+            if (lane < kRespawnWords) {
+                if (((reset >> r) & 1) && a.finished) a.finished[(first + r) * kRespawnWords + lane] = rec[lane];
+                rec[lane] = 0.0;
+            }
+        }
+    }
+    for (unsigned long long set = reset; set != 0; set &= set - 1) {
+        const int64_t rb = first + __builtin_ctzll(set);
+        for (int k = 0; k < a.n_regions; ++k) {
+            const RespawnRegion& g = a.region[k];
+            const bool slots = g.runs > 1, narrow = (g.run_bytes & 7) != 0;
+            const int word = narrow ? 4 : 8;
+            const int count = slots ? g.runs : g.run_bytes / word;
+            const int64_t step = slots ? g.run_step : word;
+            char* const p = g.base + rb * g.robot_stride;
+            if (narrow) { for (int e = lane; e < count; e += 64) *reinterpret_cast<uint32_t*>(p + e * step) = 0u; }
+            else { for (int e = lane; e < count; e += 64) *reinterpret_cast<unsigned long long*>(p + e * step) = 0ull; }
+        }
+    }
+}
+
+// rows: robot b's row of dst becomes the template's (src_rows 1: row 0; else row b) where its mask value selects the entry -- `when` bit 0 on mask 1, bit 1 on mask 2
+struct RespawnRow { char* dst; const char* src; int32_t row_bytes, broadcast, when, wide; };   // wide: row_bytes and both pointers are multiples of 8
+struct RespawnRowsArgs {
+    int32_t n, n_rows;
+    const uint8_t* mask;
+    RespawnRow row[kRespawnRowsMax];
+};
+__global__ __launch_bounds__(64) void a1mpc_respawn_rows_kernel(const RespawnRowsArgs a) {
+    const int lane = static_cast<int>(threadIdx.x);
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 64;
+    if (first >= a.n) return;   // (whole wave)
+    const int m = first + lane < a.n ? a.mask[first + lane] : 0;
+    const unsigned long long on1 = __ballot(m == 1), on2 = __ballot(m == 2);
+    if ((on1 | on2) == 0) return;
+    for (int k = 0; k < a.n_rows; ++k) {
+        const RespawnRow& g = a.row[k];
+        const unsigned long long sel = ((g.when & 1) ? on1 : 0ull) | ((g.when & 2) ? on2 : 0ull);
+        for (unsigned long long set = sel; set != 0; set &= set - 1) {
+            const int64_t rb = first + __builtin_ctzll(set);
+            char* const d = g.dst + rb * g.row_bytes;
+            const char* const s = g.src + (g.broadcast ? 0 : rb * g.row_bytes);
+            if (g.wide) {
+                const int count = g.row_bytes >> 3;
+                for (int e = lane; e < count; e += 64) reinterpret_cast<unsigned long long*>(d)[e] = reinterpret_cast<const unsigned long long*>(s)[e];
+            } else {
+                for (int e = lane; e < g.row_bytes; e += 64) d[e] = s[e];
+            }
+        }
+    }
+}
+
 // ---- what a horizon compiled in has: its record sizes and the entry points of its a1mpc_k_*.hip units
 struct HorizonOps {
     int horizon;
@@ -5113,6 +5215,146 @@ a1mpc_status a1mpc_episode_summary_batch(a1mpc_handle h, int32_t n, const double
     A1_STAGE_LAUNCH(launch_episode_summary(h, n, d_episode, h->d_episode_ws, s));
     A1_HIP(hipMemcpyAsync(summary_out, h->d_episode_ws, kEpSummary * sizeof(double), hipMemcpyDeviceToHost, s));
     return sg.finish();
+}
+
+// ---- respawn behind the C ABI: a1mpc_respawn_kernel and a1mpc_respawn_rows_kernel.  The launcher turns the handle's state blocks into the kernel's table of regions: the
+// bytes of robot b that the whole-handle reset of each A1MPC_RESPAWN_* bit zeroes, and no others; a block that is not allocated yet gives no region
+void a1mpc_default_respawn_config(a1mpc_respawn_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof *c);
+    c->codes = 0xEu; c->max_ticks = 0; c->hold_ticks = 10; c->what = A1MPC_RESPAWN_EKF | A1MPC_RESPAWN_CONTACT | A1MPC_RESPAWN_SENSOR | A1MPC_RESPAWN_WARM;
+}
+static int respawn_regions(a1mpc_handle h, uint32_t what, RespawnRegion* g) {
+    const int64_t N = h->max_batch, D = sizeof(double);
+    int k = 0;
+    auto block = [&](void* base, int64_t bytes) { g[k++] = RespawnRegion{static_cast<char*>(base), bytes, 0, static_cast<int32_t>(bytes), 1}; };
+    auto slots = [&](void* base, int64_t word, int32_t runs) { g[k++] = RespawnRegion{static_cast<char*>(base), word, word * N, static_cast<int32_t>(word), runs}; };
+    if ((what & A1MPC_RESPAWN_EKF) && h->d_ekf_state) block(h->d_ekf_state, kEkfState * D);
+    if ((what & A1MPC_RESPAWN_CONTACT) && h->d_ct_state) {   // (make_contact_args: records, leg rings, terrain rings)
+        char* const rec = reinterpret_cast<char*>(h->d_ct_state);
+        char* const leg = rec + N * static_cast<int64_t>(sizeof(CtRecord));
+        block(rec, sizeof(CtRecord));
+        block(leg, kCtLegRing * D);
+        slots(leg + N * static_cast<int64_t>(kCtLegRing) * D, D, kTerrainWindow);
+    }
+    if ((what & A1MPC_RESPAWN_SENSOR) && h->d_sensor_filt && h->d_sensor_cursor) {   // (every slot the allocation holds, as a1mpc_reset_sensor_state)
+        slots(h->d_sensor_filt, D, kImuFilters * (h->sensor_alloc_window + 2));
+        slots(h->d_sensor_cursor, sizeof(int32_t), 2);
+    }
+    if (what & A1MPC_RESPAWN_WARM) {
+        const int64_t H = h->cfg.horizon;
+        block(h->d_wx, 12 * H * D); block(h->d_wy, 20 * H * D); block(h->d_rho, D);
+        if (h->d_carry) block(h->d_carry, static_cast<int64_t>(carry_stride(h->cfg.horizon)) * D);
+    }
+    static_assert(kRespawnRegions >= 10, "one region per block above");
+    return k;
+}
+static bool respawn_overlap(const void* p, size_t bp, const void* q, size_t bq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + bq && b < a + bp;
+}
+static const char* invalid_respawn_reset(a1mpc_handle h, int32_t n, const uint8_t* mask, uint32_t what) {
+    if (!h) return "null handle";
+    if (!mask) return "null mask";
+    if (n < 0) return "negative n";
+    if (what & ~0xFu) return "what has bits that are no A1MPC_RESPAWN_* block";
+    return nullptr;
+}
+static const char* invalid_respawn(a1mpc_handle h, const a1mpc_respawn_config* cfg, int32_t n, const double* episode, const int32_t* life, const double* finished_out,
+                                   const uint8_t* mask_out) {
+    if (!h) return "null handle";
+    if (!cfg) return "null a1mpc_respawn_config";
+    if (!episode) return "null episode";
+    if (!life) return "null life";
+    if (!mask_out) return "null mask_out";
+    if (n < 0) return "negative n";
+    if (cfg->what & ~0xFu) return "a1mpc_respawn_config.what has bits that are no A1MPC_RESPAWN_* block";
+    if (cfg->codes & ~0xEu) return "a1mpc_respawn_config.codes has bits that are no end code (1 .. 3)";
+    if (cfg->hold_ticks < 0) return "a1mpc_respawn_config.hold_ticks must not be negative";
+    if (cfg->max_ticks >= (1ull << 53)) return "a1mpc_respawn_config.max_ticks must be below 2^53";
+    const size_t N = static_cast<size_t>(n), be = N * kRespawnWords * sizeof(double);
+    if (finished_out && respawn_overlap(finished_out, be, episode, be)) return "finished_out overlaps episode";
+    if (respawn_overlap(mask_out, N, episode, be)) return "mask_out overlaps episode";
+    return nullptr;
+}
+static void launch_respawn(a1mpc_handle h, RespawnArgs& a, uint32_t what, hipStream_t s) {
+    a.n_regions = respawn_regions(h, what, a.region);
+    if ((what & A1MPC_RESPAWN_EKF) != 0) h->ekf_ready_n = 0;   // (the next EKF launch runs the init kernel again; it returns at once for a robot whose flag word is not zero)
+    if (a.mask && a.n_regions == 0) return;
+    hipLaunchKernelGGL(a1mpc_respawn_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(a.n) + 63) / 64)), dim3(64), 0, s, a);
+}
+static RespawnArgs respawn_args(int32_t n, const uint8_t* mask, const a1mpc_respawn_config* cfg, double* episode, int32_t* life, double* finished_out, uint8_t* mask_out) {
+    RespawnArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n = n; a.mask = mask; a.record = episode; a.life = life; a.finished = finished_out; a.mask_out = mask_out;
+    if (cfg) { a.codes = cfg->codes; a.hold_ticks = cfg->hold_ticks; a.max_ticks = static_cast<double>(cfg->max_ticks); }
+    return a;
+}
+a1mpc_status a1mpc_respawn_reset_batch_device(a1mpc_handle h, int32_t n, const uint8_t* d_mask, uint32_t what, void* hip_stream) {
+    if (const char* bad = invalid_respawn_reset(h, n, d_mask, what)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    RespawnArgs a = respawn_args(n, d_mask, nullptr, nullptr, nullptr, nullptr, nullptr);
+    A1_STAGE_LAUNCH(launch_respawn(h, a, what, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_respawn_reset_batch(a1mpc_handle h, int32_t n, const uint8_t* mask, uint32_t what) {
+    if (const char* bad = invalid_respawn_reset(h, n, mask, what)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    const uint8_t* d_mask = sg.in(mask, 1);
+    A1_STAGED(sg);
+    RespawnArgs a = respawn_args(n, d_mask, nullptr, nullptr, nullptr, nullptr, nullptr);
+    A1_STAGE_LAUNCH(launch_respawn(h, a, what, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_respawn_batch_device(a1mpc_handle h, const a1mpc_respawn_config* cfg, int32_t n, double* d_episode, int32_t* d_life, double* d_finished_out,
+                                        uint8_t* d_mask_out, void* hip_stream) {
+    if (const char* bad = invalid_respawn(h, cfg, n, d_episode, d_life, d_finished_out, d_mask_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    RespawnArgs a = respawn_args(n, nullptr, cfg, d_episode, d_life, d_finished_out, d_mask_out);
+    A1_STAGE_LAUNCH(launch_respawn(h, a, cfg->what, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_respawn_batch(a1mpc_handle h, const a1mpc_respawn_config* cfg, int32_t n, double* episode, int32_t* life, double* finished_out, uint8_t* mask_out) {
+    if (const char* bad = invalid_respawn(h, cfg, n, episode, life, finished_out, mask_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    double* d_episode = sg.inout(episode, kRespawnWords);
+    double* d_life = sg.inout(reinterpret_cast<double*>(life), 1);   // (two int32 per robot: one staging word)
+    double* d_finished = finished_out ? sg.inout(finished_out, kRespawnWords) : nullptr;   // (in as well: a row the call does not write keeps its bits)
+    uint8_t* d_mask = sg.out(mask_out, 1);
+    A1_STAGED(sg);
+    RespawnArgs a = respawn_args(n, nullptr, cfg, d_episode, reinterpret_cast<int32_t*>(d_life), d_finished, d_mask);
+    A1_STAGE_LAUNCH(launch_respawn(h, a, cfg->what, s));
+    return sg.finish();
+}
+a1mpc_status a1mpc_respawn_rows_device(a1mpc_handle h, int32_t n, const uint8_t* d_mask, const a1mpc_respawn_rows* rows, int32_t n_rows, void* hip_stream) {
+    if (!h) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!d_mask) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null mask");
+    if (n < 0) return fail(A1MPC_ERR_INVALID_ARGUMENT, "negative n");
+    if (n_rows < 0 || n_rows > A1MPC_RESPAWN_ROWS_MAX) return fail(A1MPC_ERR_INVALID_ARGUMENT, "n_rows outside 0 .. A1MPC_RESPAWN_ROWS_MAX");
+    if (!rows) return fail(A1MPC_ERR_INVALID_ARGUMENT, "null rows");
+    RespawnRowsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n = n; a.n_rows = n_rows; a.mask = d_mask;
+    for (int k = 0; k < n_rows; ++k) {
+        const a1mpc_respawn_rows& r = rows[k];
+        const std::string at = "a1mpc_respawn_rows[" + std::to_string(k) + "].";
+        if (!r.dst) return fail(A1MPC_ERR_INVALID_ARGUMENT, at + "dst is null");
+        if (!r.src) return fail(A1MPC_ERR_INVALID_ARGUMENT, at + "src is null");
+        if (r.row_bytes < 1 || r.row_bytes > 4096) return fail(A1MPC_ERR_INVALID_ARGUMENT, at + "row_bytes outside 1 .. 4096");
+        if (r.src_rows != 1 && r.src_rows < n) return fail(A1MPC_ERR_INVALID_ARGUMENT, at + "src_rows is neither 1 nor >= n");
+        if (r.when == 0 || (r.when & ~3u)) return fail(A1MPC_ERR_INVALID_ARGUMENT, at + "when must be 1, 2 or 3");
+        const bool broadcast = r.src_rows == 1;
+        const size_t rb = static_cast<size_t>(r.row_bytes), N = static_cast<size_t>(n);
+        if (respawn_overlap(r.dst, N * rb, r.src, (broadcast ? 1 : N) * rb)) return fail(A1MPC_ERR_INVALID_ARGUMENT, at + "dst overlaps src");
+        const bool wide = ((reinterpret_cast<uintptr_t>(r.dst) | reinterpret_cast<uintptr_t>(r.src) | static_cast<uintptr_t>(r.row_bytes)) & 7) == 0;
+        a.row[k] = RespawnRow{static_cast<char*>(r.dst), static_cast<const char*>(r.src), r.row_bytes, broadcast ? 1 : 0, static_cast<int32_t>(r.when), wide ? 1 : 0};
+    }
+    A1_STAGE_DEVICE(hip_stream);
+    if (n_rows == 0) return A1MPC_OK;
+    A1_STAGE_LAUNCH(hipLaunchKernelGGL(a1mpc_respawn_rows_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 63) / 64)), dim3(64), 0, s, a));
+    return A1MPC_OK;
 }
 #undef A1_STAGE_BEGIN
 #undef A1_STAGE_DEVICE

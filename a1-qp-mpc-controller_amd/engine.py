@@ -83,6 +83,15 @@ class EpisodeConfig(C.Structure):  # a1mpc_episode_config: when an episode ends 
     _fields_ = [("min_up", C.c_double), ("min_height", C.c_double)]
 
 
+class RespawnConfig(C.Structure):  # a1mpc_respawn_config: which ended episodes start again, the time limit, the hold while the estimator is primed, the blocks cleared
+    _fields_ = [("codes", C.c_uint32), ("max_ticks", C.c_uint64), ("hold_ticks", C.c_int32), ("what", C.c_uint32)]
+
+
+class RespawnRows(C.Structure):  # a1mpc_respawn_rows: one entry of the table of a1mpc_respawn_rows_device
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("row_bytes", C.c_int32), ("src_rows", C.c_int32), ("when", C.c_uint32)]
+
+
+RESPAWN_EKF, RESPAWN_CONTACT, RESPAWN_SENSOR, RESPAWN_WARM, RESPAWN_ROWS_MAX = 1, 2, 4, 8, 16   # A1MPC_RESPAWN_*
 EPISODE_WORDS = 16   # doubles per robot of an episode record; all zero is the start of an episode
 EPISODE_FIELDS = ("ticks", "end_tick_p1", "end_code", "vel_err_sum", "height_err_sum", "tilt_max", "est_pos_err_sum", "est_vel_err_sum", "est_vel_err_max", "effort_sum",
                   "fz_max", "solver_bad", "reach_bad", "x0", "y0", "dist2")
@@ -112,7 +121,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_episode_config", "a1mpc_episode_update_batch", "a1mpc_episode_update_batch_device", "a1mpc_episode_summary_batch",
+EXPORTS = ["a1mpc_default_respawn_config", "a1mpc_respawn_reset_batch", "a1mpc_respawn_reset_batch_device", "a1mpc_respawn_batch", "a1mpc_respawn_batch_device",
+           "a1mpc_respawn_rows_device", "a1mpc_default_episode_config", "a1mpc_episode_update_batch", "a1mpc_episode_update_batch_device", "a1mpc_episode_summary_batch",
            "a1mpc_episode_summary_batch_device", "a1mpc_default_noise_config", "a1mpc_sensor_noise_batch", "a1mpc_sensor_noise_batch_device",
            "a1mpc_ground_step_batch", "a1mpc_ground_step_batch_device", "a1mpc_touch_sensors_batch", "a1mpc_touch_sensors_batch_device",
            "a1mpc_default_walk_config", "a1mpc_walk_step_batch", "a1mpc_walk_step_batch_device", "a1mpc_walk_sensors_batch", "a1mpc_walk_sensors_batch_device",
@@ -279,6 +289,14 @@ def load_library(path=None):
         lib.a1mpc_episode_update_batch_device.restype = C.c_int
         lib.a1mpc_episode_summary_batch.argtypes = [vp, i32, dp, dp]; lib.a1mpc_episode_summary_batch.restype = C.c_int
         lib.a1mpc_episode_summary_batch_device.argtypes = [vp, i32, vpp, vpp, vpp]; lib.a1mpc_episode_summary_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_respawn_batch"):   # (respawn; an older build bound by hand for an A/B lacks it)
+        u32 = C.c_uint32; u8p = C.POINTER(C.c_uint8); i32p = C.POINTER(C.c_int32)
+        lib.a1mpc_default_respawn_config.argtypes = [C.POINTER(RespawnConfig)]; lib.a1mpc_default_respawn_config.restype = None
+        lib.a1mpc_respawn_reset_batch.argtypes = [vp, i32, u8p, u32]; lib.a1mpc_respawn_reset_batch.restype = C.c_int
+        lib.a1mpc_respawn_reset_batch_device.argtypes = [vp, i32, vpp, u32, vpp]; lib.a1mpc_respawn_reset_batch_device.restype = C.c_int
+        lib.a1mpc_respawn_batch.argtypes = [vp, C.POINTER(RespawnConfig), i32, dp, i32p, dp, u8p]; lib.a1mpc_respawn_batch.restype = C.c_int
+        lib.a1mpc_respawn_batch_device.argtypes = [vp, C.POINTER(RespawnConfig), i32, vpp, vpp, vpp, vpp, vpp]; lib.a1mpc_respawn_batch_device.restype = C.c_int
+        lib.a1mpc_respawn_rows_device.argtypes = [vp, i32, vpp, C.POINTER(RespawnRows), i32, vpp]; lib.a1mpc_respawn_rows_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_control_tick_balance_device"):   # (the balance-QP controller on the device; an older build bound by hand for an A/B lacks it)
         lib.a1mpc_default_balance_gains.argtypes = [C.POINTER(BalanceGains)]; lib.a1mpc_default_balance_gains.restype = None
         lib.a1mpc_balance_wrench_batch.argtypes = [vp, C.POINTER(BalanceGains), i32] + [dp] * 10; lib.a1mpc_balance_wrench_batch.restype = C.c_int
@@ -852,6 +870,58 @@ class Engine:
         """device pointers, asynchronous on `stream`: d_summary (20 float64) receives the summary of the n records of d_episode"""
         rc = self.lib.a1mpc_episode_summary_batch_device(self._h, int(n), _dev(d_episode), _dev(d_summary), C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_episode_summary_batch_device")
+
+    # ---- respawn: a robot whose episode is over gets its lane back on the device -- the decision with its hold, the masked reset of the handle's state, the caller's rows ----
+    def respawn_config(self, **fields):
+        """a1mpc_default_respawn_config (codes 0xE, max_ticks 0, hold_ticks 10, what 0xF) with `fields` overridden"""
+        rc = RespawnConfig(); self.lib.a1mpc_default_respawn_config(C.byref(rc))
+        for k, v in fields.items():
+            if k not in [f for f, _ in RespawnConfig._fields_]:
+                raise KeyError(k)
+            setattr(rc, k, v)
+        return rc
+
+    def respawn_reset(self, mask, what=15):
+        """a1mpc_respawn_reset_batch: the state of every robot b with mask[b] & 1 is cleared in the blocks `what` names (RESPAWN_*); synchronises like every host entry"""
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        _check(self.lib, self.lib.a1mpc_respawn_reset_batch(self._h, mask.shape[0], _u8p(mask), int(what)), "a1mpc_respawn_reset_batch")
+
+    def respawn_reset_device(self, n, d_mask, what=15, stream=None):
+        """device pointer, asynchronous on `stream`: d_mask is n bytes"""
+        rc = self.lib.a1mpc_respawn_reset_batch_device(self._h, int(n), _dev(d_mask), int(what), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_respawn_reset_batch_device")
+
+    def respawn(self, episode, life, finished=None, config=None):
+        """a1mpc_respawn_batch: episode (n, 16) float64, life (n, 2) int32 and, when given, finished (n, 16) float64 are changed IN PLACE (writeable C-contiguous
+        arrays) -> mask (n,) uint8: 0 left alone, 1 respawned, 2 held"""
+        for a, dt, w, name in ((episode, np.float64, EPISODE_WORDS, "episode"), (life, np.int32, 2, "life"), (finished, np.float64, EPISODE_WORDS, "finished")):
+            if a is None and name == "finished":
+                continue
+            if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable and a.ndim == 2 and a.shape == (episode.shape[0], w)):
+                raise ValueError(f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape (n, {w}): it is changed in place")
+        mask = np.zeros(episode.shape[0], dtype=np.uint8)
+        rc = config if config is not None else self.respawn_config()
+        _check(self.lib, self.lib.a1mpc_respawn_batch(self._h, C.byref(rc), episode.shape[0], _dp(episode), _ip(life), _dp(finished), _u8p(mask)), "a1mpc_respawn_batch")
+        return mask
+
+    def respawn_device(self, n, d_episode, d_life, d_mask, d_finished=None, config=None, stream=None):
+        """device pointers, asynchronous on `stream`: d_episode n x 16 float64, d_life n x 2 int32, d_mask n bytes (out), d_finished n x 16 float64 or None"""
+        rc = config if config is not None else self.respawn_config()
+        st = self.lib.a1mpc_respawn_batch_device(self._h, C.byref(rc), int(n), _dev(d_episode), _dev(d_life), _dev(d_finished), _dev(d_mask),
+                                                 C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, st, "a1mpc_respawn_batch_device")
+
+    def respawn_rows_device(self, n, d_mask, rows, stream=None):
+        """a1mpc_respawn_rows_device: rows is a list of (dst, src, when) torch tensors on the device -- dst has n rows at the least, src one row (the template of every
+        robot) or n at the least; the row is dst's row in bytes; when: 1 on respawn, 2 on a held tick, 3 on both"""
+        table = (RespawnRows * max(len(rows), 1))()
+        for k, (dst, src, when) in enumerate(rows):
+            row_bytes = dst[0].numel() * dst.element_size()
+            if not (dst.is_contiguous() and src.is_contiguous() and src.numel() * src.element_size() % row_bytes == 0):
+                raise ValueError(f"rows[{k}]: dst and src must be contiguous, src a whole number of dst's rows")
+            table[k] = RespawnRows(dst.data_ptr(), src.data_ptr(), row_bytes, src.numel() * src.element_size() // row_bytes, int(when))
+        rc = self.lib.a1mpc_respawn_rows_device(self._h, int(n), _dev(d_mask), table, len(rows), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_respawn_rows_device")
 
     def last_control_tick_ms(self):
         ms = C.c_float(0); fused = C.c_int32(0)

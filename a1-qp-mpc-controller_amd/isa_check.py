@@ -237,6 +237,7 @@ NO_SCRATCH += ("a1mpc_sensor_synthesis_kernel",)   # sensor synthesis: the quate
 NO_SCRATCH += ("a1mpc_walk_step_kernel", "a1mpc_walk_sensors_kernel")   # the walking plant and its sensors: the two kernels above with a few more selects, the same run-time loop bound
 NO_SCRATCH += ("a1mpc_walk_step_ground_kernel", "a1mpc_walk_sensors_touch_kernel")   # sloped ground and touch: third copies of the two above with three more words per robot through LDS, one byte per lane and two more selects
 NO_SCRATCH += ("a1mpc_sensor_noise_kernel",)   # sensor noise: ten unrolled Philox rounds in registers, the four words of a draw and the draw index are compile-time indices
+NO_SCRATCH += ("a1mpc_respawn_kernel", "a1mpc_respawn_rows_kernel")   # respawn: both walk a table in the kernel arguments under a wave-uniform index; no per-lane array at all
 NO_SCRATCH += ("a1mpc_episode_update_kernel", "a1mpc_episode_reduce_kernel")   # episode record and summary: the record's 16 words and the summary's 20 are register arrays under compile-time indices; a lane's four words leave through selects
 # ... and kernels that may park a few long-lived values (pointers, the rotation) in scratch ACROSS their loops but not inside them: (pattern, scratch bytes, scratch instructions in loops)
 BOUNDED_SCRATCH = (("a1mpc_setup_gen_kernelILi14E", 64, 0), ("a1mpc_setup_gen_kernelILi16E", 64, 0), ("a1mpc_setup_gen_kernelILi20E", 128, 8))   # (two wavefronts per SIMD: 256 registers; a dozen long-lived values wait in scratch while the Ruiz passes run)

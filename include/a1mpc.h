@@ -999,7 +999,7 @@ a1mpc_status a1mpc_sensor_noise_batch_device(a1mpc_handle h, const a1mpc_noise_c
  * x[2i + 1] until one value is left.  It does not depend on the launch geometry (every summed word of a record is at least +0, so the + (+0) of the radix-64 levels
  * the kernel uses is exact).  No atomics: a1mpc_episode_reduce_kernel runs level by level, 64 rows per wavefront, the levels separated by launches on the stream; the
  * partials live in a workspace sized from max_batch at a1mpc_create.
- * What it is not: no reset of the handle's state (EKF, contact filters) for a robot that fell -- a fallen robot's record freezes, its loop goes on; no quantiles or
+ * What it is not: no reset of the handle's state (EKF, contact filters) for a robot that fell -- a fallen robot's record freezes, its loop goes on (a1mpc_respawn_batch below starts it again); no quantiles or
  * histograms; sums, not means (divide by word 6 or word 0 yourself); one batch, not merged across shards or handles.
  * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch, every array left untouched: a null handle (first), cfg, state, R_world
  * or episode; a stride other than 12 / 13 / 22; n < 0; min_up outside [-1, 1] or not finite; min_height not finite; tick >= 2^53 - 1; half of a pair (root_pos /
@@ -1021,6 +1021,78 @@ a1mpc_status a1mpc_episode_update_batch_device(a1mpc_handle h, const a1mpc_episo
                                                const int32_t* d_status, const uint8_t* d_reach, double* d_episode, void* hip_stream);
 a1mpc_status a1mpc_episode_summary_batch(a1mpc_handle h, int32_t n, const double* episode, double* summary_out);
 a1mpc_status a1mpc_episode_summary_batch_device(a1mpc_handle h, int32_t n, const double* d_episode, double* d_summary_out, void* hip_stream);
+
+/*
+ * Respawn: a robot whose episode is over gets its lane back, on the device.  Behind the episode update of a closed loop, a1mpc_respawn_batch_device decides per robot
+ * whether its episode is to start again, clears that robot's state in the handle and holds it for a few ticks while its estimator is primed;
+ * a1mpc_respawn_rows_device then puts the caller's own rows back.  Every robot is on its own episode clock (word 0 of its record) and nothing is read back per tick.
+ * A family of its own, a1mpc_respawn_*, two kernels (a1mpc_respawn_kernel, a1mpc_respawn_rows_kernel): the entries above are unchanged.
+ *
+ * MASKED RESET.  a1mpc_respawn_reset_batch(_device): for every robot b < n with mask[b] & 1, every byte of that robot's state that the whole-handle reset of each bit
+ * of `what` zeroes is zeroed, and no other byte of the handle changes:
+ *   A1MPC_RESPAWN_EKF      a1mpc_reset_ekf_state: the robot's row of the filter state (x, P and the flag word; a zero flag word is a new filter, which the init kernel
+ *                          takes on the next EKF launch).  With n > 0 the handle forgets which robots have been initialised, so that the next EKF launch runs its init
+ *                          kernel again: that kernel returns at once for every robot whose flag word is not zero
+ *   A1MPC_RESPAWN_CONTACT  a1mpc_reset_contact_state: its contact record, its leg windows and its word of every slot of the terrain window
+ *   A1MPC_RESPAWN_SENSOR   a1mpc_reset_sensor_state: its word of every slot, sum and correction of the six IMU filters, its count and cursor.  The window the state was
+ *                          built with stays: a masked reset does not license another imu_window
+ *   A1MPC_RESPAWN_WARM     a1mpc_reset_warm_start: its carried iterates and rho and, once allocated, its record of the update path's carry.  The queue order of the next
+ *                          solve stays (it is scheduling only: results do not depend on it)
+ * A block that is not allocated yet is skipped.  From the call on a reset robot gives, bit for bit in every output of every entry, what the same batch position gives on
+ * a handle on which the whole-handle resets were called at that point; every other robot gives what it gives on a handle that saw no reset.  The _device entry is
+ * asynchronous on hip_stream (NULL = the handle's), ordered like every other _device entry, and does not synchronise -- the whole-handle resets do.
+ *
+ * DECISION.  a1mpc_respawn_batch(_device), once per tick behind a1mpc_episode_update_batch(_device):
+ *   in / out  episode       n x 16 doubles, the records of the episode update
+ *             life          n x 2 int32, owned by the caller: [hold, episodes_done]; all zero = nobody held, nothing finished
+ *   out       finished_out  n x 16 doubles, optional: the record an episode ended with, taken when its robot is respawned; a row the call does not write keeps its bits
+ *             mask_out      n bytes: 0 left alone, 1 respawned, 2 held
+ * Per robot, in this order:  (1) hold > 0: HELD -- every word of the record becomes +0, hold -= 1, mask_out = 2.  The record is not consulted: a held robot is stepped
+ * and then put back (rows, below), so whatever the step made of it, a NaN included, ends no episode.  (2) Otherwise, if end_code == c for a c of 1 .. 3 with bit c of
+ * cfg->codes set, or end_code == 0, cfg->max_ticks > 0 and ticks >= max_ticks: RESPAWNED -- the 16 words go to finished_out[b] when given, the record becomes +0, hold =
+ * cfg->hold_ticks, episodes_done += 1, mask_out = 1, and the robot's state in the handle is cleared as by the masked reset with cfg->what, in the same launch.
+ * (3) Otherwise mask_out = 0 and nothing else is written.  Copies, comparisons and integer arithmetic only.
+ * With life[b][0] = hold_ticks at the start of a run the first hold_ticks ticks are held: the priming of a fresh estimator on an unstepped plant, per robot.  After a
+ * respawn the robot is held for exactly hold_ticks ticks and its record starts from zero on the first free tick.
+ *
+ * ROWS.  a1mpc_respawn_rows_device: the loop's other state (the plant's rows, the tick's carried arrays, the command state, imu_bias) is the caller's, and only the
+ * caller knows its spawn values.  For each of n_rows <= A1MPC_RESPAWN_ROWS_MAX table entries and every robot b < n whose mask value selects the entry (`when` bit 0: on
+ * mask 1, bit 1: on mask 2; any other mask value selects nothing), row b of dst becomes row b of src (src_rows >= n) or its row 0 (src_rows == 1): copied, never
+ * computed; every other byte is untouched.  8-byte words where row_bytes and both pointers are multiples of 8, bytes otherwise.  Typically the plant's rows carry when =
+ * 3 (put back on every held tick: an unstepped plant) and the rest when = 1.  There is no host-pointer variant: a host caller has mask_out and its own arrays.
+ *
+ * What it is not: one handle only, not the pipeline or the sharded handles (a1mpc_sharded_handle gives a shard's handle for the masked reset); spawn poses are the
+ * caller's templates, nothing is randomised; finished_out keeps only a robot's latest finished record; a held robot's plant step is computed and discarded.
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch, every array left untouched: a null handle (first), cfg, episode, life,
+ * mask_out, mask or rows; n < 0; `what` or codes with unknown bits (bit 0 of codes included); hold_ticks < 0; max_ticks >= 2^53; n_rows outside 0 .. 16; a null dst or
+ * src; row_bytes outside 1 .. 4096; src_rows neither 1 nor >= n; `when` 0 or with unknown bits; dst overlapping its src; finished_out or mask_out overlapping episode.
+ * n > max_batch is A1MPC_ERR_BATCH_TOO_LARGE.  n == 0 is A1MPC_OK and launches nothing.
+ */
+#define A1MPC_RESPAWN_EKF 1u
+#define A1MPC_RESPAWN_CONTACT 2u
+#define A1MPC_RESPAWN_SENSOR 4u
+#define A1MPC_RESPAWN_WARM 8u
+#define A1MPC_RESPAWN_ROWS_MAX 16
+typedef struct a1mpc_respawn_config {
+    uint32_t codes;      /* bit c: an episode that ended with end_code c (1 non-finite, 2 tilt, 3 height) is respawned */
+    uint64_t max_ticks;  /* > 0: a live episode whose ticks has reached it is respawned too (a time limit); 0: none */
+    int32_t hold_ticks;  /* ticks a respawned robot is held at its spawn rows while its estimator is primed */
+    uint32_t what;       /* A1MPC_RESPAWN_* bits cleared for a respawned robot */
+} a1mpc_respawn_config;
+typedef struct a1mpc_respawn_rows {
+    void* dst;
+    const void* src;
+    int32_t row_bytes;
+    int32_t src_rows;    /* 1: one template row for every robot; >= n: row b */
+    uint32_t when;       /* bit 0: on mask 1 (respawned), bit 1: on mask 2 (held) */
+} a1mpc_respawn_rows;
+void a1mpc_default_respawn_config(a1mpc_respawn_config* cfg);   /* codes 0xE, max_ticks 0, hold_ticks 10, what 0xF */
+a1mpc_status a1mpc_respawn_reset_batch(a1mpc_handle h, int32_t n, const uint8_t* mask, uint32_t what);
+a1mpc_status a1mpc_respawn_reset_batch_device(a1mpc_handle h, int32_t n, const uint8_t* d_mask, uint32_t what, void* hip_stream);
+a1mpc_status a1mpc_respawn_batch(a1mpc_handle h, const a1mpc_respawn_config* cfg, int32_t n, double* episode, int32_t* life, double* finished_out, uint8_t* mask_out);
+a1mpc_status a1mpc_respawn_batch_device(a1mpc_handle h, const a1mpc_respawn_config* cfg, int32_t n, double* d_episode, int32_t* d_life, double* d_finished_out,
+                                        uint8_t* d_mask_out, void* hip_stream);
+a1mpc_status a1mpc_respawn_rows_device(a1mpc_handle h, int32_t n, const uint8_t* d_mask, const a1mpc_respawn_rows* rows, int32_t n_rows, void* hip_stream);
 
 /*
  * Debug / verification: the dense QP data the reference's ConvexMpc keeps in its public members after calculate_qp_mats
