@@ -223,9 +223,10 @@ def balance_params(qp=None, settings=None, **over):
     return p
 
 
-def balance_solve(sc, n=None, settings=None, **over):
+def balance_solve(sc, n=None, settings=None, qp=None, **over):
+    """qp: the QP's constants, dict(Q (6), R, mu, F_min, F_max) (balance_params); None: the reference's"""
     n = len(sc["root_acc"]) if n is None else n
-    P = balance_params(None, settings, **over)
+    P = balance_params(qp, settings, **over)
     grf = np.zeros((n, 12)); f = np.zeros((n, 12)); iters = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
     rc = lib().a1mpc_emu_balance(C.byref(P), n, _p(sc["root_acc"]), _p(sc["R"]), _p(sc["Rz"]), _p(sc["foot"]),
                                  _p(sc["contact"], C.c_uint8), _p(grf), _p(f), _p(iters, C.c_int32), _p(status, C.c_int32))

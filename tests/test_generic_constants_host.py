@@ -9,7 +9,7 @@ test of the suite.
 3. the oracle's formation against the reference's ConvexMpc compiled verbatim (oracle/_ref), the bars of tests/test_ref_pin.py's GPU counterpart;
 4. the solver text on host fibers (tests/emu) against the oracle, bar 1e-8, same iteration, status and factor passes on every QP; the Ruiz sweep's early stop exact;
 5. the host-compiled caller-side kernel texts against their numpy restatements, each with the comparison its own host test uses.
-The balance QP has weights of its own (tests/tools/soak_settings_balance.py soaks them) and is not part of this file."""
+The balance QP has weights of its own: tests/test_balance_constants_host.py is this file's counterpart for them."""
 import numpy as np
 import pytest
 

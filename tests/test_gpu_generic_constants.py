@@ -5,8 +5,8 @@ wrong pair of inertia words, swap or drop q[3] / q[4], index r by leg, or be han
 Yardsticks and bars are the ones the suite already holds: the oracle through gpu_common.held_to_oracle (TOL_FORCE_N; the cap on QPs settled by the 80-bit build is shown to
 hold for the oracle alone on these very batches by tests/test_generic_constants_host.py), the reference's ConvexMpc at 1e-12 / 1e-10, HS.BAR, and bit for bit where the
 existing test of an entry is.  Every solver test first shows, on the yardstick and for its own batch, that each of the seven generic_variants() moves the forces by more than
-100 x TOL_FORCE_N on at least half of the QPs looked at: a pass cannot come from inputs that hide the constants.  The balance QP has weights of its own
-(tests/tools/soak_settings_balance.py) and is not part of this file."""
+100 x TOL_FORCE_N on at least half of the QPs looked at: a pass cannot come from inputs that hide the constants.  The balance QP has weights of its own: tests/test_gpu_balance_constants.py
+holds it to a generic set of those."""
 import ctypes as C
 
 import numpy as np

@@ -26,6 +26,10 @@ class MpcParamsX(C.Structure):  # orc_mpc_params
     _fields_ = [("horizon", C.c_int32), ("dt", LD), ("mu", LD), ("fz_min", LD), ("fz_max", LD), ("q", LD * 13), ("r", LD * 12), ("mass", LD), ("inertia", LD * 9)]
 
 
+class QpParamsX(C.Structure):   # orc_qp_params: the balance QP's constants
+    _fields_ = [("Qw", LD * 6), ("R", LD), ("mu", LD), ("F_min", LD), ("F_max", LD)]
+
+
 _lib = None
 
 
@@ -86,3 +90,19 @@ def mpc_solve(pr, st, x0, xref, Rw, foot, contact, foot_stride=0, contact_stride
                         C.c_int(int(contact_stride)), _ldp(grf), _ldp(u), None if wx is None else _ldp(wx), None if wy is None else _ldp(wy),
                         C.byref(rho), C.byref(info))
     return dict(grf=grf.astype(np.float64), u=u.astype(np.float64), iters=int(info.iters), status=int(info.status))
+
+
+def qp_params(qp):
+    """QpParamsX of a constants dict (Q (6), R, mu, F_min, F_max: balance_common.DEFAULT_BALANCE / GENERIC_BALANCE)"""
+    p = QpParamsX(); p.R = qp["R"]; p.mu = qp["mu"]; p.F_min = qp["F_min"]; p.F_max = qp["F_max"]
+    for i, v in enumerate(qp["Q"]): p.Qw[i] = v
+    return p
+
+
+def balance_solve(qp, st, root_acc, Rw, Rz, foot, contact):
+    """one balance QP (orc_balance_solve in extended precision; qp: a QpParamsX, st: a SettingsX): dict(grf, f_world, iters, status)"""
+    grf = np.zeros(12, np.longdouble); f = np.zeros(12, np.longdouble); info = InfoX()
+    ct = np.ascontiguousarray(contact, dtype=np.uint8)
+    ACC, RW, RZ, FT = _ld(root_acc), _ld(Rw), _ld(Rz), _ld(foot)
+    lib().orc_balance_solve(C.byref(qp), C.byref(st), _ldp(ACC), _ldp(RW), _ldp(RZ), _ldp(FT), ct.ctypes.data_as(C.POINTER(C.c_uint8)), _ldp(grf), _ldp(f), C.byref(info))
+    return dict(grf=grf.astype(np.float64), f_world=f.astype(np.float64), iters=int(info.iters), status=int(info.status))
