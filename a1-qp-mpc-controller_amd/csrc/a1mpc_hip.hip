@@ -449,7 +449,9 @@ __global__ __launch_bounds__(256) void a1mpc_balance_wrench_kp_kernel(const Wren
 //             reference words, then writes its three state words over them).  Rows of 52 doubles: the 8 QPs of a half wave start 40 banks apart (mod 64), the reads of a
 //             component are conflict-free.  3 * 16 * 52 doubles = 19 968 B per wave: eight waves per CU.
 //   bits      contraction off, fma() where a product feeds a sum: the results do not depend on where the compiler places the code, nor on the number of QPs in the call.
-//   dead lanes (QPs >= n of the last wave) read the wave's first QP, take part in every shuffle and store nothing, neither to LDS nor to memory.
+//   dead lanes (QPs >= n of the last wave) read the wave's first QP, take part in every shuffle and store nothing, neither to LDS nor to memory.  Of the X rows they read
+//             their OWN row, not the first QP's: that QP's lanes write their states over it, and only the wave's lock step would order the two.  A dead lane's row is
+//             UNINITIALISED LDS (hs_load / hs_store touch the live rows alone, nothing ever writes it): the read is meant, and its value is discarded with the lane's cost.
 struct HorizonStatesArgs {
     int32_t n, H, foot_stride;
     double dt, mass, inertia[9], q[12], r[12];
@@ -580,7 +582,7 @@ __global__ __launch_bounds__(64) void a1mpc_horizon_states_kernel(const HorizonS
                 const double got = __shfl_xor(l >= 2 ? x[k] : snd[k], 2, 64);
                 w[k] = l >= 2 ? got + snd[k] : got;   // lanes 2 / 3: (leg 0 + leg 1) + (leg 2 + leg 3)
             }
-            double* xo = X + row + tt * 13 + 3 * l;
+            double* xo = X + qw * kHsRow + tt * 13 + 3 * l;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 double xn = fma(M[3 * k + 2], w[2], fma(M[3 * k + 1], w[1], fma(M[3 * k], w[0], x[k])));

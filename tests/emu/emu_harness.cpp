@@ -12,6 +12,42 @@
 #include "a1mpc_solver.hpp"
 #include "a1mpc_tables.hpp"
 
+// -DA1_EMU_ONLY_H=<h>: keep the `case`s of one horizon (tests/test_host_sanitizers.py: the whole file is too large to compile under AddressSanitizer as one unit, one
+// horizon is not).  Without it every horizon is compiled, as ever.
+#ifdef A1_EMU_ONLY_H
+#define A1_EMU_HAS(h) ((h) == (A1_EMU_ONLY_H))
+#else
+#define A1_EMU_HAS(h) 1
+#endif
+// Under AddressSanitizer every switch of a fiber is announced, so that the sanitizer knows which stack it is on (it reports overflows of a stack it was not told about).
+// The macros carry their own semicolons: without the sanitizer the build has not one token more than before.
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#define A1_EMU_ASAN 1
+#endif
+#endif
+#if defined(__SANITIZE_ADDRESS__) && !defined(A1_EMU_ASAN)
+#define A1_EMU_ASAN 1
+#endif
+#ifdef A1_EMU_ASAN
+#include <sanitizer/common_interface_defs.h>
+#define A1_EMU_FIBER_STATE void* fake_main; void* fake[kLanes]; const void* main_bottom; size_t main_size;
+#define A1_EMU_TO_LANE(s, l) __sanitizer_start_switch_fiber(&(s)->fake_main, (s)->stacks[l], kStack);
+#define A1_EMU_IN_MAIN(s) __sanitizer_finish_switch_fiber((s)->fake_main, nullptr, nullptr);
+#define A1_EMU_LANE_STARTS(s) __sanitizer_finish_switch_fiber(nullptr, &(s)->main_bottom, &(s)->main_size);
+#define A1_EMU_TO_MAIN(s, l) __sanitizer_start_switch_fiber(&(s)->fake[l], (s)->main_bottom, (s)->main_size);
+#define A1_EMU_IN_LANE(s, l) __sanitizer_finish_switch_fiber((s)->fake[l], nullptr, nullptr);
+#define A1_EMU_LANE_ENDS(s) __sanitizer_start_switch_fiber(nullptr, (s)->main_bottom, (s)->main_size);
+#else
+#define A1_EMU_FIBER_STATE
+#define A1_EMU_TO_LANE(s, l)
+#define A1_EMU_IN_MAIN(s)
+#define A1_EMU_LANE_STARTS(s)
+#define A1_EMU_TO_MAIN(s, l)
+#define A1_EMU_IN_LANE(s, l)
+#define A1_EMU_LANE_ENDS(s)
+#endif
+
 namespace a1mpc {
 
 thread_local int emu_lane = 0;
@@ -31,14 +67,17 @@ struct Sched {
     long gen[kLanes], xgen[kLanes], qgen[kLanes];            // how many of each this lane has published
     void (*fn)(void*);
     void* arg;
+    A1_EMU_FIBER_STATE
 };
 thread_local Sched* g_s = nullptr;
 
 void trampoline() {
     Sched* s = g_s;
     const int l = emu_lane;
+    A1_EMU_LANE_STARTS(s)
     s->fn(s->arg);
     s->finished[l] = true;
+    A1_EMU_LANE_ENDS(s)
     swapcontext(&s->ctx[l], &s->main_ctx);
 }
 // yield until every lane lo..hi-1 has published exchange number g (counters cnt)
@@ -51,7 +90,9 @@ void wait_for(Sched* s, int l, const long* cnt, long g, int lo, int hi) {
             all = all && cnt[x] >= g;
         }
         if (all) return;
+        A1_EMU_TO_MAIN(s, l)
         swapcontext(&s->ctx[l], &s->main_ctx);
+        A1_EMU_IN_LANE(s, l)
         emu_lane = l;
     }
 }
@@ -118,7 +159,9 @@ static void run_row(void (*fn)(void*), void* arg, int lanes = 16, bool retire_ok
         for (int l = 0; l < lanes; ++l) {
             if (s.finished[l]) continue;
             emu_lane = l;
+            A1_EMU_TO_LANE(&s, l)
             swapcontext(&s.main_ctx, &s.ctx[l]);
+            A1_EMU_IN_MAIN(&s)
             if (!s.finished[l]) ++alive;
         }
         if (!alive) break;
@@ -227,7 +270,23 @@ extern "C" void a1mpc_emu_set_twin(int on) { a1mpc::g_emu_twin = on; }
 extern "C" void a1mpc_emu_set_contact_stride(int stride) { a1mpc::g_emu_contact_stride = stride; }
 extern "C" void a1mpc_emu_set_carry(double* carry) { a1mpc::g_emu_carry = carry; }
 extern "C" int a1mpc_emu_carry_stride(int horizon) {
-    switch (horizon) { case 10: return a1mpc::Carry<10>::STRIDE; case 16: return a1mpc::Carry<16>::STRIDE; case 20: return a1mpc::Carry<20>::STRIDE; case 4: return a1mpc::Carry<4>::STRIDE; case 12: return a1mpc::Carry<12>::STRIDE; }
+    switch (horizon) {
+#if A1_EMU_HAS(10)
+        case 10: return a1mpc::Carry<10>::STRIDE;
+#endif
+#if A1_EMU_HAS(16)
+        case 16: return a1mpc::Carry<16>::STRIDE;
+#endif
+#if A1_EMU_HAS(20)
+        case 20: return a1mpc::Carry<20>::STRIDE;
+#endif
+#if A1_EMU_HAS(4)
+        case 4: return a1mpc::Carry<4>::STRIDE;
+#endif
+#if A1_EMU_HAS(12)
+        case 12: return a1mpc::Carry<12>::STRIDE;
+#endif
+    }
     return 0;
 }
 
@@ -294,12 +353,24 @@ extern "C" int a1mpc_emu_solve_split(const a1mpc::DeviceParams* P, int horizon, 
     const bool twin = nrows < 0;  // nrows < 0: -nrows persistent main / twin PAIRS of rows (the device's persistent kernel)
     if (twin) nrows = -nrows;
     switch (horizon) {
+#if A1_EMU_HAS(1)
         case 1: a1mpc::run_split<1>(a, nrows); return 0;
+#endif
+#if A1_EMU_HAS(10)
         case 10: a1mpc::run_split<10>(a, nrows, twin); return 0;
+#endif
+#if A1_EMU_HAS(16)
         case 16: a1mpc::run_split<16>(a, nrows, twin); return 0;
+#endif
+#if A1_EMU_HAS(20)
         case 20: a1mpc::run_split<20>(a, nrows, twin); return 0;
+#endif
+#if A1_EMU_HAS(4)
         case 4: a1mpc::run_split<4>(a, nrows, twin); return 0;     // two of the extended horizons (csrc/a1mpc_common.hpp, A1MPC_FAST_HORIZONS): the shortest, and one beyond 10
+#endif
+#if A1_EMU_HAS(12)
         case 12: a1mpc::run_split<12>(a, nrows, twin); return 0;
+#endif
     }
     return -1;
 }
@@ -344,14 +415,21 @@ extern "C" int a1mpc_emu_solve_gen_split(const a1mpc::DeviceParams* P, int horiz
     a.P = *P; a.n = n; a.x0 = x0; a.xref = xref; a.R = R; a.foot = foot; a.contact = contact; a.grf = grf; a.u_full = u_full;
     a.iters = iters; a.status = status; a.nfact = nfact; a.foot_stride = foot_stride; a.contact_stride = contact_stride;
     switch (horizon) {
+#if A1_EMU_HAS(10)
         case 10: a1mpc::run_split_gen<10>(a, nrows); return 0;
+#endif
+#if A1_EMU_HAS(16)
         case 16: a1mpc::run_split_gen<16>(a, nrows); return 0;
+#endif
+#if A1_EMU_HAS(20)
         case 20: a1mpc::run_split_gen<20>(a, nrows); return 0;
+#endif
     }
     return -1;
 }
 extern "C" int a1mpc_emu_solve_ticks(const a1mpc::DeviceParams* P, int horizon, int n, const double* tick, const double* R,
                                      const double* foot, const uint8_t* contact, double* grf, double* u_full, int32_t* iters, int32_t* status) {
+#if A1_EMU_HAS(10)
     using namespace a1mpc;
     if (horizon != 10) return -1;
     std::vector<double> tab(2 * 10 * 10);
@@ -367,29 +445,47 @@ extern "C" int a1mpc_emu_solve_ticks(const a1mpc::DeviceParams* P, int horizon, 
         run_row(job_entry<10>, &j);
     }
     return 0;
+#else
+    return -1;
+#endif
 }
 extern "C" int a1mpc_emu_solve(const a1mpc::DeviceParams* P, int horizon, int n, const double* x0, const double* xref, const double* R,
                                const double* foot, const uint8_t* contact, double* grf, double* u_full, double* warm_x,
                                double* warm_y, double* rho, int32_t* iters, int32_t* status, int32_t* nfact) {
     switch (horizon) {
+#if A1_EMU_HAS(1)
         case 1: a1mpc::run_batch<1>(P, n, x0, xref, R, foot, contact, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(4)
         case 4: a1mpc::run_batch<4>(P, n, x0, xref, R, foot, contact, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(12)
         case 12: a1mpc::run_batch<12>(P, n, x0, xref, R, foot, contact, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(10)
         case 10: a1mpc::run_batch<10>(P, n, x0, xref, R, foot, contact, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(16)
         case 16: a1mpc::run_batch<16>(P, n, x0, xref, R, foot, contact, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(20)
         case 20: a1mpc::run_batch<20>(P, n, x0, xref, R, foot, contact, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
     }
     return -1;
 }
+#if A1_EMU_HAS(1)
 namespace a1mpc {
 static void balance_entry(void* a) {
     Job<1>* j = static_cast<Job<1>*>(a);
     solve_row<1, kModeBalance>(*j->P, j->tab, j->io, j->lds);
 }
 }  // namespace a1mpc
+#endif
 extern "C" int a1mpc_emu_balance(const a1mpc::DeviceParams* P, int n, const double* root_acc, const double* R, const double* Rz,
                                  const double* foot, const uint8_t* contact, double* grf, double* f_world, int32_t* iters,
                                  int32_t* status) {
+#if A1_EMU_HAS(1)
     using namespace a1mpc;
     double tab[2];
     fill_gamma_beta_table(1, tab);
@@ -406,6 +502,9 @@ extern "C" int a1mpc_emu_balance(const a1mpc::DeviceParams* P, int n, const doub
         run_row(balance_entry, &j);
     }
     return 0;
+#else
+    return -1;
+#endif
 }
 namespace a1mpc {
 template <int H>
@@ -470,10 +569,18 @@ extern "C" int a1mpc_emu_solve_gen(const a1mpc::DeviceParams* P, int horizon, in
                                    const double* foot, int foot_stride, const uint8_t* contact, int contact_stride, double* grf, double* u_full,
                                    double* warm_x, double* warm_y, double* rho, int32_t* iters, int32_t* status, int32_t* nfact) {
     switch (horizon) {
+#if A1_EMU_HAS(4)
         case 4: a1mpc::run_gen<4>(P, n, x0, xref, R, foot, foot_stride, contact, contact_stride, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(10)
         case 10: a1mpc::run_gen<10>(P, n, x0, xref, R, foot, foot_stride, contact, contact_stride, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(16)
         case 16: a1mpc::run_gen<16>(P, n, x0, xref, R, foot, foot_stride, contact, contact_stride, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
+#if A1_EMU_HAS(20)
         case 20: a1mpc::run_gen<20>(P, n, x0, xref, R, foot, foot_stride, contact, contact_stride, grf, u_full, warm_x, warm_y, rho, iters, status, nfact); return 0;
+#endif
     }
     return -1;
 }
