@@ -171,7 +171,23 @@ A1_DEV double dot_bc(const double (&m)[N], double x, double init = 0.0) {
 }
 // below this rho the dual residual at a checkpoint is dominated by the x-update's backward error unless c P x + c g is carried (RowSolver::advance, the CAREFUL variant of admm_iteration)
 constexpr double kRhoCareful = 1e-3;
-constexpr double kSigGeneralPath = 2251799813685248.0;   // 2^51: tag of a pattern signature (Carry<H>::SIG) written by the general path; its hash stays below 2^50
+// pattern signature of the update path (Carry<H>::SIG; RowSolver::setup, "pattern change"): sum over the step pairs of K2^t K1^s word_st mod 2^64
+constexpr unsigned long long kSigK1 = 0x9E3779B97F4A7C15ull, kSigK2 = 0xC2B2AE3D27D4EB4Full;   // (odd)
+constexpr unsigned long long kSigColumns = 0x249249249ull;                                     // bit 3 b of the twelve columns b
+// the coefficient of one class of step pairs: 0: s != t, max(s,t) < H - 1 | 1: s != t, max(s,t) = H - 1 | 2: s = t < H - 1 | 3: s = t = H - 1
+constexpr unsigned long long sig_class_sum(int H, int cls) {
+    unsigned long long sum = 0, kt = 1;
+    for (int t = 0; t < H; ++t) {
+        unsigned long long ks = 1;
+        for (int s = 0; s < H; ++s) {
+            const int m = s > t ? s : t;
+            if ((s == t ? 2 : 0) + (m == H - 1 ? 1 : 0) == cls) sum += kt * ks;
+            ks *= kSigK1;
+        }
+        kt *= kSigK2;
+    }
+    return sum;
+}
 // gamma_st = alpha_st / beta_st and beta_st = H - max(s,t) never grow with t for fixed s (csrc/a1mpc_tables.hpp; the quotients are compared as integers,
 // rounding them to double is monotone)
 constexpr bool gamma_beta_monotone(int H) {
@@ -335,8 +351,9 @@ struct LayoutSetup {
 template <int H>
 struct Carry {
     static constexpr int C = 0, D = 1, E0 = D + 12 * H, E1 = E0 + 12 * H, G = E1 + 12 * H, Z0 = G + 12 * H, Z1 = Z0 + 12 * H;
-    // SIG [12 lanes]: which entries of my rows of U and V were non-zero -- the sparsity pattern of the previous tick's Hessian as osqp-eigen's updateHessianMatrix
-    // compares it (the reference's hessian is dense.sparseView(), S/ConvexMpc.cpp:211: exact zeros are not stored); see RowSolver::setup, "pattern change"
+    // SIG [12 lanes]: which entries of my rows of the dense Hessian were non-zero, folded into one number per lane that both paths form alike -- the sparsity pattern of
+    // the previous tick's Hessian as osqp-eigen's updateHessianMatrix compares it (the reference's hessian is dense.sparseView(), S/ConvexMpc.cpp:211: exact zeros are
+    // not stored); see RowSolver::setup, "pattern change"
     static constexpr int SIG = Z1 + 12 * H;
     static constexpr int STRIDE = SIG + 12 + 1;  // (even)
 };
@@ -804,44 +821,89 @@ struct RowSolver {
         // Pattern change.  osqp-eigen's updateHessianMatrix takes osqp_update_P only while the upper-triangular triplets of hessian.sparseView() keep their pattern; when
         // exact zeros of the reference's dense B_qp'QB_qp appear or vanish it reads the workspace iterates, clears the solver, initialises it again (fresh scaling with
         // the CURRENT data, rho back to settings.rho) and warm-starts it with those iterates through osqp_warm_start_x / _y -- which scale what they are given, and
-        // what they are given are the previous solve's SCALED iterates (oracle/a1mpc_oracle.c osqp_solve_impl, `reinit`).  Block (s,t) of the Hessian is alpha_st U + beta_st V with
-        // alpha_st = 0 exactly where max(s,t) = H - 1, so the pattern of P is a function of the zero patterns of U and V: my rows' 24 flags are the signature.
+        // what they are given are the previous solve's SCALED iterates (oracle/a1mpc_oracle.c osqp_solve_impl, `reinit`).
+        // The signature is a hash of the pattern, entry by entry, whichever path forms the QP.  Entry ((s,a),(t,b)) of the dense Hessian is a sum of products
+        // 2 q_r B_qp[(i,r),(s,a)] B_qp[(i,r),(t,b)] over the steps i >= max(s,t) and the state rows r, so it is stored exactly when one weighted row meets both columns:
+        //   omega rows (any i):      q_{6+c} != 0 and B~w_s[c][a] != 0 and B~w_t[c][b] != 0          vel rows (any i):      q_{9+k} != 0 and comp_a = comp_b = k
+        //   rpy rows (i > max(s,t)): q_c != 0 and (T B~w_s)[c][a] != 0 and (T B~w_t)[c][b] != 0      pos rows (i > max(s,t)): q_{3+k} != 0 and comp_a = comp_b = k
+        // or it lies on the diagonal under a non-zero r_a.  A flag that changes under a zero weight, or where another row keeps the entry, is no change (until this rule the
+        // general path compared unweighted flags, a superset, and the two paths' signatures were not comparable: a tick that switched paths never re-initialised).
+        // Each lane folds its rows of the pattern -- 12 H words of 12 entries, one bit per entry at 3 b -- into sum_st K2^t K1^s word_st mod 2^64 and keeps the top 52 bits,
+        // exact in a double: a 52-bit hash of 12 H x 12 pattern bits, so two different patterns compare equal with a chance of about 2^-52 per comparison (accepted).  The rule
+        // takes a sum of weighted non-zero products for non-zero where the oracle tests the number it formed: the two differ only where such a sum cancels to exactly 0.0,
+        // a set of measure zero in the feet and the attitude.  On the fast path the words take four values (max(s,t) < H - 1 or not, s = t or not) and the sum collapses to four compile-time coefficients;
+        // the general path with the same feet on every step gives the same number.
         [[maybe_unused]] bool reinit = false;
         [[maybe_unused]] double sig = 0.0;
         if constexpr (UPD && MODE == kModeMpc && H > 1) {
+            using u64 = unsigned long long;
+            const unsigned qu = (P.q2[0] != 0.0 ? 1u : 0u) | (P.q2[1] != 0.0 ? 2u : 0u) | (P.q2[2] != 0.0 ? 4u : 0u);   // weighted rpy rows
+            const unsigned qv = (P.q2[6] != 0.0 ? 1u : 0u) | (P.q2[7] != 0.0 ? 2u : 0u) | (P.q2[8] != 0.0 ? 4u : 0u);   // weighted omega rows
+            const int cq = act ? comp : 0;
+            const u64 same = act ? (0x8040201ull << (3 * cq)) : 0ull;                  // the columns of my force component, one per leg
+            const u64 wpos = P.q2[3 + cq] != 0.0 ? same : 0ull, wvel = P.q2[9 + cq] != 0.0 ? same : 0ull;
+            const u64 wdiag = (act && r2a != 0.0) ? (1ull << (3 * ci)) : 0ull;
+            // the 3-bit row flags of all twelve columns in one word (column b at bit 3 b): an exact sum over the lanes, below 2^36
+            auto pack = [&](unsigned f) {
+                const double s = row_allsum(act ? ldexp(static_cast<double>(f), 3 * ci) : 0.0);
+                const unsigned hi = static_cast<unsigned>(s * 0x1p-18);
+                const unsigned lo = static_cast<unsigned>(s - static_cast<double>(hi) * 0x1p18);
+                return (static_cast<u64>(hi) << 18) | static_cast<u64>(lo);
+            };
+            // which columns share a flagged row with mine: bit 3 b
+            auto meet = [&](unsigned mine, u64 all) {
+                const u64 m = (kSigColumns * static_cast<u64>(mine)) & all;
+                return (m | (m >> 1) | (m >> 2)) & kSigColumns;
+            };
+            u64 hs = 0;
             if constexpr (GEN) {
-                // General path (round 5): every block (s,t) has its own U_st, V_st; an entry of the reference's dense Hessian is structurally zero exactly when the omega /
-                // rpy rows of B~w_s[:,a] and B~w_t[:,b] have no common non-zero (and the velocity / position rows do not match), so the pattern is a function of the zero
-                // patterns of my columns of the per-step tables B~w_s and T B~w_s: 6 flags per step and lane, folded into one exactly representable number (< 2^50).
-                // A change of these flags is a SUPERSET of the changes osqp-eigen sees (a flag can change under a zero weight without touching the Hessian's pattern);
-                // for inputs in general position neither ever changes.
-                unsigned long long hsh = 0;
+                // General path: my columns' flags of every step, 3 bits per step (as step_factors forms T B~w_s)
+                static_assert(3 * H <= 64, "myU / myV hold three flags per horizon step in one 64-bit word");
+                u64 myU = 0, myV = 0;
                 static_for<H>([&](auto S) {
-                    unsigned v = 0;
                     double bwS[3];
                     bw_at(A1_CV(S), bwS);
                     const double tbS[3] = {fma(cy, bwS[0], sy * bwS[1]), fma(-sy, bwS[0], cy * bwS[1]), bwS[2]};   // my column of T B~w_s, as step_factors forms it
+                    unsigned u = 0, v = 0;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         v |= (bwS[c] != 0.0 ? 1u : 0u) << c;
-                        v |= (tbS[c] != 0.0 ? 1u : 0u) << (3 + c);
+                        u |= (tbS[c] != 0.0 ? 1u : 0u) << c;
                     }
-                    hsh = (hsh * 67ull + v + 1ull) & ((1ull << 50) - 1ull);
+                    myU |= static_cast<u64>(u & qu) << (3 * A1_CV(S));
+                    myV |= static_cast<u64>(v & qv) << (3 * A1_CV(S));
                 });
-                sig = act ? static_cast<double>(hsh) + kSigGeneralPath : 0.0;   // (+ 2^51: "written by the general path", exact in a double)
+#pragma clang loop unroll(disable)
+                for (int t = H - 1; t >= 0; --t) {
+                    const u64 Ut = pack(static_cast<unsigned>(myU >> (3 * t)) & 7u), Vt = pack(static_cast<unsigned>(myV >> (3 * t)) & 7u);
+                    u64 in = 0;
+#pragma clang loop unroll(disable)
+                    for (int s = H - 1; s >= 0; --s) {
+                        u64 w = meet(static_cast<unsigned>(myV >> (3 * s)) & 7u, Vt) | wvel;
+                        if ((s > t ? s : t) < H - 1) w |= meet(static_cast<unsigned>(myU >> (3 * s)) & 7u, Ut) | wpos;
+                        if (s == t) w |= wdiag;
+                        in = in * kSigK1 + w;
+                    }
+                    hs = hs * kSigK2 + in;
+                }
             } else {
-                unsigned bits = 0;
-                static_for<12>([&](auto B) { bits |= (U[B] != 0.0 ? 1u : 0u) << A1_CV(B); bits |= (V[B] != 0.0 ? 1u : 0u) << (12 + A1_CV(B)); });
-                sig = act ? static_cast<double>(bits) : 0.0;
+                unsigned u = 0, v = 0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    v |= (Bt[c] != 0.0 ? 1u : 0u) << c;
+                    u |= (TB[c] != 0.0 ? 1u : 0u) << c;
+                }
+                const u64 Ua = pack(u & qu), Va = pack(v & qv);
+                const u64 wB = meet(v & qv, Va) | wvel;               // max(s,t) = H - 1: no step behind both
+                const u64 wA = wB | meet(u & qu, Ua) | wpos;
+                hs = wA * sig_class_sum(H, 0) + wB * sig_class_sum(H, 1) + (wA | wdiag) * sig_class_sum(H, 2) + (wB | wdiag) * sig_class_sum(H, 3);
             }
+            sig = act ? static_cast<double>(hs >> 12) : 0.0;
             if (upd) {
-                // The two paths encode the pattern differently (24 flags of U / V | a hash of the per-step tables' flags, tagged 2^51): signatures are only comparable when
-                // the same path wrote both.  A handle that alternates between the paths (foot_stride / yaw_A toggled between ticks) keeps the UPDATE path across the switch --
-                // everything else in the carry (previous scalings, gradient, z) means the same on both, and the reference's persistent solver takes osqp_update_P whenever
-                // the dense Hessian keeps its pattern, which inputs in general position do on either path (until round 6 every switch took the pattern-change branch)
+                // A handle that alternates between the paths (foot_stride / yaw_A toggled between ticks) keeps the UPDATE path across the switch unless the pattern changes with it:
+                // everything else in the carry (previous scalings, gradient, z) means the same on both
                 const double prev = act ? io.carry[CR::SIG + ci] : 0.0;
-                const bool same_path = (prev >= kSigGeneralPath) == (sig >= kSigGeneralPath);
-                reinit = row_allmax((same_path && prev != sig) ? 1.0 : 0.0) > 0.0;
+                reinit = row_allmax(prev != sig ? 1.0 : 0.0) > 0.0;
             }
         }
         [[maybe_unused]] double gq[(UPD && MODE == kModeMpc && H > 1 && !GEN) ? H : 1];   // the gradient the cost normalisation sees: the previous tick's on the update path

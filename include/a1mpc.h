@@ -100,13 +100,15 @@ typedef struct a1mpc_config {
                                          gradient still in the workspace and starts from the previous solve's SCALED (x, z, y) as they are.  The handle then
                                          also carries the previous scalings, gradient and z of every problem.  Restated from OSQP 0.6's update functions
                                          (oracle: orc_mpc_solve_update); every horizon > 1, on the fast path and on (round 5; round 6: at every batch size) the general
-                                         path (per-step feet / contact schedules / its own A_c yaw: a1mpc_solve_batch_strided; its pattern-change test reads the
-                                         zero patterns of the per-step tables, a superset of the changes osqp-eigen sees).  Horizon 1 (the balance QP, which the
+                                         path (per-step feet / contact schedules / its own A_c yaw: a1mpc_solve_batch_strided).  Horizon 1 (the balance QP, which the
                                          reference cold-starts anyway) behaves like 1: a1mpc_last_warm_start_mode reports which semantics a solve actually ran.
                                          When the sparsity pattern of the reference's Hessian (dense.sparseView(), S/ConvexMpc.cpp:211: exact zeros are not stored)
                                          changes from one tick to the next, osqp-eigen cannot take osqp_update_P: updateHessianMatrix clears the solver, initialises
                                          it again (rho back to cfg.rho, fresh scaling) and warm-starts it with the workspace's scaled iterates -- reproduced per
-                                         problem (the pattern is a function of the zero patterns of the two 12x12 blocks the Hessian is made of).  A tick solved
+                                         problem.  The decision is the same on both paths and across a switch between them: an entry of the dense Hessian is
+                                         stored exactly when a state row with a non-zero weight meets both of its columns of B_qp, so the entries are compared
+                                         as that rule gives them -- a zero of B~ that appears or vanishes under a zero weight, or where another weighted row
+                                         keeps the entry, is no change (tests/test_gpu_update_reinit.py, tests/test_update_reinit_host.py).  A tick solved
                                          in another mode or through the general path's split pipeline drops the carried workspace: the next tick is a fresh set-up
                                          warm-started from (x, y, rho).  (An a1mpc_warm_start injection does NOT drop it since round 4: see there.) */
 } a1mpc_config;
