@@ -1616,6 +1616,261 @@ __global__ __launch_bounds__(64) void a1mpc_walk_sensors_touch_kernel(const Walk
     if (lane < live * 4) a.quat[first * 4 + lane] = QO[lane];
     if (lane < live * 3) { a.acc[first * 3 + lane] = AO[lane]; a.gyro[first * 3 + lane] = GO[lane]; }
 }
+
+// ---- height-field terrain (a1mpc_heightfield_step_batch, a1mpc_heightfield_sample_batch): the ground step above with ONE gridded field of heights in place of the
+// plane per robot -- stairs, kerbs, rough ground -- reached by every robot through an optional origin row (ox, oy, oz), so that several terrains in one batch are tiles
+// of one field.  A fourth copy, not a template: the three step kernels above keep their text, their code objects and their host emulation byte for byte.  The rule
+// hf(X, Y) is stated in include/a1mpc.h and restated elementwise in tests/heightfield_ref.py; both kernels below call the one function that holds it.
+//   lanes, memory, bits, dead lanes   those of a1mpc_walk_step_ground_kernel; a robot's origin row takes the plane's place in wave-private LDS.  The field stays in global
+//             memory: a lane gathers one node (cell-constant) or four (bilinear) under its foot and as many under its body, after pos' and r' are known.  The two gathers
+//             are issued together, so the kernel has ONE exposed memory round trip behind its input loads.  A dead lane samples node (0, 0) and stores nothing.
+struct HfField {   // a1mpc_heightfield as the kernels take it: the reciprocals of the spacings are made once on the host
+    const double* H;
+    double x0, y0, inv_dx, inv_dy;
+    int32_t nx, ny, interp;
+};
+// hf(X, Y) in the header's operation order.  interp is passed apart from f so that a caller's branch on it folds here; shifted: an origin row is given (ox, oy, oz);
+// live false: the lane belongs to no robot and reads node (0, 0).  Only the clamped cx, cy -- finite, in [0, nx - 1] and [0, ny - 1] -- are ever converted to an integer
+__device__ __forceinline__ double hf_sample(const HfField& f, const int interp, const bool live, const bool shifted, const double ox, const double oy, const double oz,
+                                            const double X, const double Y) {
+#pragma clang fp contract(off)
+    double ux, uy;
+    if (shifted) { ux = ((X - ox) - f.x0) * f.inv_dx; uy = ((Y - oy) - f.y0) * f.inv_dy; }
+    else { ux = (X - f.x0) * f.inv_dx; uy = (Y - f.y0) * f.inv_dy; }
+    const bool valid = (ux == ux) && (uy == uy);
+    const double mx = static_cast<double>(f.nx - 1), my = static_cast<double>(f.ny - 1);
+    double cx = ux > 0.0 ? ux : 0.0, cy = uy > 0.0 ? uy : 0.0;   // (a NaN goes to 0)
+    cx = cx < mx ? cx : mx; cy = cy < my ? cy : my;
+    cx = live ? cx : 0.0; cy = live ? cy : 0.0;
+    const int64_t nx = f.nx;
+    double h;
+    if (interp == 0) {
+        const int64_t i = static_cast<int>(cx), j = static_cast<int>(cy);
+        h = f.H[j * nx + i];
+    } else {
+        int i = static_cast<int>(cx), j = static_cast<int>(cy);
+        i = i < f.nx - 1 ? i : f.nx - 2; j = j < f.ny - 1 ? j : f.ny - 2;
+        const double tx = cx - static_cast<double>(i), ty = cy - static_cast<double>(j);
+        const double* p = f.H + (static_cast<int64_t>(j) * nx + i);
+        const double h00 = p[0], h10 = p[1], h01 = p[nx], h11 = p[nx + 1];
+        const double a = h00 + tx * (h10 - h00), b = h01 + tx * (h11 - h01);
+        h = a + ty * (b - a);
+    }
+    double top = valid ? h : __builtin_nan("");
+    if (shifted) top = top + oz;
+    return top;
+}
+struct WalkHeightfieldArgs {
+    WalkArgs w;             // (w.flat_ground / w.ground_z are not read)
+    HfField f;
+    const double* origin;   // may be null
+    uint8_t* touch;
+    double* ground_out;     // may be null
+};
+__global__ __launch_bounds__(64) void a1mpc_walk_step_heightfield_kernel(const WalkHeightfieldArgs ha) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double hlds[kPlState + kPlR + kPlExt + kPlR + 16 * 3];
+    double* const S = hlds; double* const RL = hlds + kPlState; double* const E = hlds + kPlState + kPlR; double* const ZL = hlds + kPlState + kPlR + kPlExt;
+    double* const GL = hlds + kPlState + kPlR + kPlExt + kPlR;
+    const WalkArgs& wa = ha.w;
+    const PlantArgs& a = wa.p;
+    const int lane = static_cast<int>(threadIdx.x), qw = lane >> 2, l = lane & 3, stride = a.stride;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
+    if (first >= a.n) return;   // (whole wave)
+    const int live = static_cast<int>(a.n - first < 16 ? a.n - first : 16);
+    const bool alive = qw < live;
+    const int q = alive ? qw : 0;
+    const int64_t b = first + q;
+    const bool track = wa.track != 0.0, shifted = ha.origin != nullptr;
+    // every load, then the LDS writes, as in the ground step; the origin rows are 48 words at most: one load per lane
+    const int cs = live * stride, cr = live * 9, ce = a.ext ? live * 6 : 0, cz = track ? cr : 0, cg = shifted ? live * 3 : 0;
+    const double *gs = a.state + first * stride, *gr = a.R + first * 9, *ge = a.ext ? a.ext + first * 6 : a.R, *gzp = track ? wa.Rz + first * 9 : a.R;
+    const double* gg = shifted ? ha.origin + first * 3 : a.R;
+    double vs[6], vr[3], ve[2], vz[3];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; vs[m] = gs[e < cs ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vr[m] = gr[e < cr ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; ve[m] = ge[e < ce ? e : 0]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; vz[m] = gzp[e < cz ? e : 0]; }
+    const double vg = gg[lane < cg ? lane : 0];
+    double r[3], f[3], y[3];
+    {
+        const double *fp = a.foot + b * 12 + 3 * l, *gp = a.grf + b * 12 + 3 * l, *tp = track ? wa.target + b * 12 + 3 * l : fp;
+        r[0] = fp[0]; r[1] = fp[1]; r[2] = fp[2]; f[0] = gp[0]; f[1] = gp[1]; f[2] = gp[2]; y[0] = tp[0]; y[1] = tp[1]; y[2] = tp[2];
+    }
+    const bool stance = a.contacts[b * 4 + l] != 0;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { const int e = lane + 64 * m; if (e < cs) S[e] = vs[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cr) RL[e] = vr[m]; }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int e = lane + 64 * m; if (e < ce) E[e] = ve[m]; }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; if (e < cz) ZL[e] = vz[m]; }
+    if (lane < cg) GL[lane] = vg;
+    WaveStage::sync();
+    double pos[3], w[3], v[3], R[9], fe[3] = {0.0, 0.0, 0.0}, te[3] = {0.0, 0.0, 0.0};
+    {
+        const double* x = S + q * stride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pos[k] = x[3 + k]; w[k] = x[6 + k]; v[k] = x[9 + k]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = RL[q * 9 + k];
+    }
+    const bool with_ext = a.ext != nullptr;
+    if (with_ext) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { fe[k] = E[q * 6 + k]; te[k] = E[q * 6 + 3 + k]; }
+    }
+    // 0: the plant step's polish of R, I_b^-1 and L
+    {
+        double E[9], Rp[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) E[3 * i + j] = (R[i] * R[j] + R[3 + i] * R[3 + j]) + R[6 + i] * R[6 + j];
+        E[0] = E[0] - 1.0; E[4] = E[4] - 1.0; E[8] = E[8] - 1.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Rp[3 * i + j] = R[3 * i + j] - 0.5 * ((R[3 * i] * E[j] + R[3 * i + 1] * E[3 + j]) + R[3 * i + 2] * E[6 + j]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rp[k];
+    }
+    double Ii[9], L[3];
+    {
+        const double* I = a.inertia;
+        const double c00 = I[4] * I[8] - I[5] * I[7], c01 = I[5] * I[6] - I[3] * I[8], c02 = I[3] * I[7] - I[4] * I[6];
+        const double id = 1.0 / ((I[0] * c00 + I[1] * c01) + I[2] * c02);
+        Ii[0] = c00 * id; Ii[1] = (I[2] * I[7] - I[1] * I[8]) * id; Ii[2] = (I[1] * I[5] - I[2] * I[4]) * id;
+        Ii[3] = c01 * id; Ii[4] = (I[0] * I[8] - I[2] * I[6]) * id; Ii[5] = (I[2] * I[3] - I[0] * I[5]) * id;
+        Ii[6] = c02 * id; Ii[7] = (I[1] * I[6] - I[0] * I[7]) * id; Ii[8] = (I[0] * I[4] - I[1] * I[3]) * id;
+        double wb[3], Iw[3];
+        A1_PL_MTV(wb, R, w); A1_PL_MV(Iw, I, wb); A1_PL_MV(L, R, Iw);
+    }
+    // the swing foot's move over the call: the walk step's
+    double d[3] = {0.0, 0.0, 0.0}, vel[3] = {0.0, 0.0, 0.0};
+    if (track) {
+        double Rz[9], p0[3], tw[3], pt[3];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rz[k] = ZL[q * 9 + k];
+        A1_PL_MTV(p0, R, r); A1_PL_MV(tw, Rz, y); A1_PL_MTV(pt, R, tw);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double dl = wa.track * (pt[k] - p0[k]);
+            d[k] = dl / static_cast<double>(a.substeps); vel[k] = dl / a.dt;
+        }
+    }
+    const double h = a.dt / static_cast<double>(a.substeps), half = h / 2.0, m = a.mass, g = a.gravity;
+    for (int step = 0; step < a.substeps; ++step) {
+        // 1 .. 6: the walk step's
+        double fw[3], F[3], T[3];
+        A1_PL_MV(fw, R, f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fw[k] = stance ? fw[k] : 0.0;
+        const double tq[3] = {r[1] * fw[2] - r[2] * fw[1], r[2] * fw[0] - r[0] * fw[2], r[0] * fw[1] - r[1] * fw[0]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            F[k] = pl_legs(fw[k]); T[k] = pl_legs(tq[k]);
+            if (with_ext) { F[k] = F[k] + fe[k]; T[k] = T[k] + te[k]; }
+        }
+        double dp[3];
+        v[0] = v[0] + h * (F[0] / m); v[1] = v[1] + h * (F[1] / m); v[2] = v[2] + h * (F[2] / m + g);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { dp[k] = h * v[k]; pos[k] = pos[k] + dp[k]; }
+        double Rn[9];
+        {
+            const double a0 = half * w[0], a1 = half * w[1], a2 = half * w[2];
+            const double s = 2.0 / (1.0 + ((a0 * a0 + a1 * a1) + a2 * a2));
+            const double Cm[9] = {1.0 - s * (a1 * a1 + a2 * a2), s * (a0 * a1 - a2), s * (a0 * a2 + a1),
+                                  s * (a0 * a1 + a2), 1.0 - s * (a0 * a0 + a2 * a2), s * (a1 * a2 - a0),
+                                  s * (a0 * a2 - a1), s * (a1 * a2 + a0), 1.0 - s * (a0 * a0 + a1 * a1)};
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Cm[3 * i] * R[j] + Cm[3 * i + 1] * R[3 + j]) + Cm[3 * i + 2] * R[6 + j];
+        }
+        {
+            double Lb[3], wb[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) L[k] = L[k] + h * T[k];
+            A1_PL_MTV(Lb, Rn, L); A1_PL_MV(wb, Ii, Lb); A1_PL_MV(w, Rn, wb);
+        }
+        {
+            double rb[3], rs[3];
+            A1_PL_MTV(rb, R, r);
+            if (track) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) rb[k] = rb[k] + d[k];
+            }
+            A1_PL_MV(rs, Rn, rb);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) r[k] = stance ? r[k] - dp[k] : rs[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    }
+    // the field, once per call, straight down: the heights under the foot and under the body are gathered together (they depend on pos' and r': the kernel's one exposed
+    // memory round trip), each branch holding both calls so that their loads stand side by side.  Then the ground step's rule: a stance foot ON the field under its own x
+    // and y, a swing foot not below it; touch: stance, or the comparison that lifted the swing foot (a NaN compares false: the foot keeps its z and touch is 0)
+    double ox = 0.0, oy = 0.0, oz = 0.0;
+    if (shifted) { ox = GL[q * 3]; oy = GL[q * 3 + 1]; oz = GL[q * 3 + 2]; }   // (the origin's words wait in LDS until here: its image is not written again)
+    const double X = pos[0] + r[0], Y = pos[1] + r[1];
+    double top, under;
+    if (ha.f.interp == 0) { top = hf_sample(ha.f, 0, alive, shifted, ox, oy, oz, X, Y); under = hf_sample(ha.f, 0, alive, shifted, ox, oy, oz, pos[0], pos[1]); }
+    else { top = hf_sample(ha.f, 1, alive, shifted, ox, oy, oz, X, Y); under = hf_sample(ha.f, 1, alive, shifted, ox, oy, oz, pos[0], pos[1]); }
+    const double gz = top - pos[2];
+    const bool lifted = r[2] < gz;
+    r[2] = stance ? gz : (lifted ? gz : r[2]);
+    const bool touch = stance || lifted;
+    const double sp = -R[6], spc = sp > 1.0 ? 1.0 : (sp < -1.0 ? -1.0 : sp);   // (a NaN stays a NaN)
+    const double roll = atan2(R[7], R[8]), pitch = asin(spc), yaw = atan2(R[3], R[0]);
+    WaveStage::sync();   // (every lane has read its inputs)
+    if (alive) {
+        double* x = S + q * stride + 3 * l;
+        x[0] = pl_pick(l, roll, pos[0], w[0], v[0]); x[1] = pl_pick(l, pitch, pos[1], w[1], v[1]); x[2] = pl_pick(l, yaw, pos[2], w[2], v[2]);
+        if (l < 3) {
+            double* o = RL + q * 9 + 3 * l;
+            o[0] = pl_pick(l, R[0], R[3], R[6], 0.0); o[1] = pl_pick(l, R[1], R[4], R[7], 0.0); o[2] = pl_pick(l, R[2], R[5], R[8], 0.0);
+            if (ha.ground_out) ha.ground_out[b * 3 + l] = l == 0 ? under : 0.0;   // the row a1mpc_episode_update_batch takes as `ground`: (height, +0, +0)
+        }
+        double *fo = a.foot_out + b * 12 + 3 * l, *vo = wa.vel_out + b * 12 + 3 * l;
+        fo[0] = r[0]; fo[1] = r[1]; fo[2] = r[2];
+        vo[0] = stance ? 0.0 : vel[0]; vo[1] = stance ? 0.0 : vel[1]; vo[2] = stance ? 0.0 : vel[2];
+        ha.touch[b * 4 + l] = touch ? uint8_t{1} : uint8_t{0};
+    }
+    WaveStage::sync();
+    double *os = a.state_out + first * stride, *orr = a.R_out + first * 9;
+#pragma unroll
+    for (int mm = 0; mm < 6; ++mm) {
+        const int e = lane + 64 * mm;
+        const int col = stride == 12 ? e % 12 : (stride == 13 ? e % 13 : e % 22);
+        if (e < cs && col < 12) os[e] = S[e];
+    }
+#pragma unroll
+    for (int mm = 0; mm < 3; ++mm) { const int e = lane + 64 * mm; if (e < cr) orr[e] = RL[e]; }
+}
+
+// hf on its own, one point per lane: what places spawn templates on the terrain, and the cheapest place to hold the edge cases of the rule
+struct HfSampleArgs {
+    HfField f;
+    int32_t n;
+    const double *xy, *origin;   // origin may be null
+    double* out;
+};
+__global__ __launch_bounds__(64) void a1mpc_heightfield_sample_kernel(const HfSampleArgs a) {
+#pragma clang fp contract(off)
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 64 + static_cast<int64_t>(threadIdx.x);
+    if (b >= a.n) return;
+    const bool shifted = a.origin != nullptr;
+    const double X = a.xy[b * 2], Y = a.xy[b * 2 + 1];
+    double ox = 0.0, oy = 0.0, oz = 0.0;
+    if (shifted) { ox = a.origin[b * 3]; oy = a.origin[b * 3 + 1]; oz = a.origin[b * 3 + 2]; }
+    a.out[b] = a.f.interp == 0 ? hf_sample(a.f, 0, true, shifted, ox, oy, oz, X, Y) : hf_sample(a.f, 1, true, shifted, ox, oy, oz, X, Y);
+}
 #undef A1_PL_MV
 #undef A1_PL_MTV
 
@@ -5021,6 +5276,162 @@ a1mpc_status a1mpc_touch_sensors_batch(a1mpc_handle h, int32_t n, const double* 
     A1_STAGED(sg);
     A1_STAGE_LAUNCH(launch_walk_sensors_touch(h, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_vel, d_touch, touch_force, rho_fix, rho_opt, d_quat, d_acc,
                                               d_gyro, d_jp, d_jv, d_ff, d_reach, d_pr, d_vr, s));
+    return sg.finish();
+}
+// ---- height-field terrain behind the C ABI: a1mpc_walk_step_heightfield_kernel and a1mpc_heightfield_sample_kernel, no handle state
+void a1mpc_default_heightfield(a1mpc_heightfield* f) {
+    if (!f) return;
+    std::memset(f, 0, sizeof *f);
+    f->nx = 0; f->ny = 0; f->x0 = 0.0; f->y0 = 0.0; f->dx = 1.0; f->dy = 1.0; f->interp = 0; f->height = nullptr;
+}
+constexpr int32_t kHfMaxNodesPerAxis = 32768;
+constexpr int64_t kHfMaxStagedNodes = int64_t{1} << 20;   // what a host-pointer entry stages per call
+// what every heightfield entry refuses of its field, or null.  Checked FIRST, in front of the handle, so that a bad field is reported whether or not a GPU is present
+static const char* invalid_heightfield(const a1mpc_heightfield* f) {
+    if (!f) return "null a1mpc_heightfield";
+    if (f->interp != 0 && f->interp != 1) return "a1mpc_heightfield.interp must be 0 or 1";
+    const int32_t least = f->interp ? 2 : 1;
+    if (f->nx < least) return "a1mpc_heightfield.nx below 1 (interp 0) or 2 (interp 1)";
+    if (f->ny < least) return "a1mpc_heightfield.ny below 1 (interp 0) or 2 (interp 1)";
+    if (f->nx > kHfMaxNodesPerAxis) return "a1mpc_heightfield.nx above 32768";
+    if (f->ny > kHfMaxNodesPerAxis) return "a1mpc_heightfield.ny above 32768";
+    if (!std::isfinite(f->dx) || !(f->dx > 0.0)) return "a1mpc_heightfield.dx must be positive and finite";
+    if (!std::isfinite(f->dy) || !(f->dy > 0.0)) return "a1mpc_heightfield.dy must be positive and finite";
+    if (!std::isfinite(f->x0)) return "a1mpc_heightfield.x0 must be finite";
+    if (!std::isfinite(f->y0)) return "a1mpc_heightfield.y0 must be finite";
+    if (!std::isfinite(1.0 / f->dx)) return "a1mpc_heightfield.dx: 1 / dx is not finite";
+    if (!std::isfinite(1.0 / f->dy)) return "a1mpc_heightfield.dy: 1 / dy is not finite";
+    if (!f->height) return "null a1mpc_heightfield.height";
+    return nullptr;
+}
+static HfField make_hf_field(const a1mpc_heightfield& f, const double* d_height) {
+    HfField k;
+    k.H = d_height; k.x0 = f.x0; k.y0 = f.y0; k.inv_dx = 1.0 / f.dx; k.inv_dy = 1.0 / f.dy; k.nx = f.nx; k.ny = f.ny; k.interp = f.interp;
+    return k;
+}
+// a host-pointer entry's copy of the field on the device: allocated, filled on `s` and freed within the call (the handle gets no state; these entries are for tests and
+// small fields).  The free waits for the device, so it is safe behind a launch that failed half way as well
+extern "C++" {
+struct HfStaged {
+    double* d = nullptr;
+    ~HfStaged() { if (d) (void)hipFree(d); }
+    a1mpc_status fill(const a1mpc_heightfield& f, hipStream_t s) {
+        const size_t bytes = static_cast<size_t>(f.nx) * static_cast<size_t>(f.ny) * sizeof(double);
+        A1_HIP(hipMalloc(&d, bytes));
+        A1_HIP(hipMemcpyAsync(d, f.height, bytes, hipMemcpyHostToDevice, s));
+        return A1MPC_OK;
+    }
+};
+}  // extern "C++"
+static const char* too_large_to_stage(const a1mpc_heightfield& f) {
+    return static_cast<int64_t>(f.nx) * f.ny > kHfMaxStagedNodes ? "a1mpc_heightfield of more than 2^20 nodes given to a host-pointer entry: use the _device entry" : nullptr;
+}
+// what the two step entries refuse, or null: the field's refusals, then the ground step's (cfg's own plane is not read and so not checked)
+static const char* invalid_heightfield_step(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                            const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* R_z, const double* foot_target,
+                                            const a1mpc_heightfield* field, const double* state_out, const double* R_world_out, const double* foot_abs_out,
+                                            const double* foot_vel_body_out, const uint8_t* touch_out) {
+    if (const char* bad = invalid_heightfield(field)) return bad;
+    if (!h) return "null handle";
+    if (!cfg) return "null a1mpc_walk_config";
+    a1mpc_walk_config c = *cfg;
+    c.flat_ground = 0; c.ground_z = 0.0;
+    if (const char* bad = invalid_walk_step(h, &c, n, state_in, state_stride, R_world, foot_abs, grf_body, contacts, R_z, foot_target, state_out, R_world_out, foot_abs_out,
+                                            foot_vel_body_out))
+        return bad;
+    if (!touch_out) return "null touch_out";
+    return nullptr;
+}
+static void launch_heightfield_step(a1mpc_handle h, const a1mpc_walk_config& cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                    const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                    const double* foot_target, const HfField& field, const double* origin, double* state_out, double* R_world_out, double* foot_abs_out,
+                                    double* foot_vel_body_out, uint8_t* touch_out, double* ground_out, hipStream_t s) {
+    WalkHeightfieldArgs g;
+    WalkArgs& w = g.w;
+    PlantArgs& a = w.p;
+    a.n = n; a.stride = state_stride; a.substeps = cfg.plant.substeps; a.dt = cfg.plant.dt; a.gravity = cfg.plant.gravity_z; a.mass = h->cfg.mass;
+    for (int i = 0; i < 9; ++i) a.inertia[i] = h->cfg.inertia_body[i];
+    a.state = state_in; a.R = R_world; a.foot = foot_abs; a.grf = grf_body; a.ext = ext_wrench; a.contacts = contacts;
+    a.state_out = state_out; a.R_out = R_world_out; a.foot_out = foot_abs_out;
+    const bool track = cfg.swing_track != 0.0;   // (-0 is no tracking either)
+    w.track = track ? cfg.swing_track : 0.0; w.ground_z = 0.0; w.flat_ground = 0;   // (cfg's plane is not read)
+    w.Rz = track ? R_z : nullptr; w.target = track ? foot_target : nullptr; w.vel_out = foot_vel_body_out;
+    g.f = field; g.origin = origin; g.touch = touch_out; g.ground_out = ground_out;
+    hipLaunchKernelGGL(a1mpc_walk_step_heightfield_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 15) / 16)), dim3(64), 0, s, g);
+}
+a1mpc_status a1mpc_heightfield_step_batch_device(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                                 const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                                 const double* d_ext_wrench, const double* d_R_z, const double* d_foot_target, const a1mpc_heightfield* field,
+                                                 const double* d_origin, double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, double* d_foot_vel_body_out,
+                                                 uint8_t* d_touch_out, double* d_ground_out, void* hip_stream) {
+    if (const char* bad = invalid_heightfield_step(h, cfg, n, d_state_in, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_R_z, d_foot_target, field,
+                                                   d_state_out, d_R_world_out, d_foot_abs_out, d_foot_vel_body_out, d_touch_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_heightfield_step(h, *cfg, n, d_state_in, state_stride, d_R_world, d_foot_abs, d_grf_body, d_contacts, d_ext_wrench, d_R_z, d_foot_target,
+                                            make_hf_field(*field, field->height), d_origin, d_state_out, d_R_world_out, d_foot_abs_out, d_foot_vel_body_out, d_touch_out,
+                                            d_ground_out, s));
+    return A1MPC_OK;
+}
+// the host-pointer entry: staged like a1mpc_ground_step_batch, and the whole field with it
+a1mpc_status a1mpc_heightfield_step_batch(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                          const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                          const double* foot_target, const a1mpc_heightfield* field, const double* origin, double* state_out, double* R_world_out,
+                                          double* foot_abs_out, double* foot_vel_body_out, uint8_t* touch_out, double* ground_out) {
+    if (const char* bad = invalid_heightfield_step(h, cfg, n, state_in, state_stride, R_world, foot_abs, grf_body, contacts, R_z, foot_target, field, state_out,
+                                                   R_world_out, foot_abs_out, foot_vel_body_out, touch_out))
+        return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (const char* big = too_large_to_stage(*field)) return fail(A1MPC_ERR_BATCH_TOO_LARGE, big);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    HfStaged hf;
+    const size_t W = static_cast<size_t>(state_stride);
+    const bool track = cfg->swing_track != 0.0;
+    double *d_state = sg.in(state_in, W), *d_R = sg.in(R_world, 9), *d_foot = sg.in(foot_abs, 12);
+    const double *d_grf = sg.in(grf_body, 12), *d_ext = ext_wrench ? sg.in(ext_wrench, 6) : nullptr;
+    const double *d_Rz = track ? sg.in(R_z, 9) : nullptr, *d_tg = track ? sg.in(foot_target, 12) : nullptr, *d_or = origin ? sg.in(origin, 3) : nullptr;
+    const uint8_t* d_ct = sg.in(contacts, 4);
+    double* d_out = (W == 12 || state_out == state_in) ? d_state : sg.in(static_cast<const double*>(state_out), W);
+    double *d_vel = sg.out(foot_vel_body_out, 12), *d_go = sg.out(ground_out, 3);
+    uint8_t* d_touch = sg.out(touch_out, 4);
+    sg.back(state_out, d_out, W); sg.back(R_world_out, d_R, 9); sg.back(foot_abs_out, d_foot, 12);
+    A1_STAGED(sg);
+    if (a1mpc_status st = hf.fill(*field, s); st != A1MPC_OK) return st;
+    A1_STAGE_LAUNCH(launch_heightfield_step(h, *cfg, n, d_state, state_stride, d_R, d_foot, d_grf, d_ct, d_ext, d_Rz, d_tg, make_hf_field(*field, hf.d), d_or, d_out, d_R,
+                                            d_foot, d_vel, d_touch, d_go, s));
+    return sg.finish();
+}
+static const char* invalid_heightfield_sample(a1mpc_handle h, const a1mpc_heightfield* field, int32_t n, const double* xy, const double* height_out) {
+    if (const char* bad = invalid_heightfield(field)) return bad;
+    if (!h) return "null handle";
+    if (n < 0) return "negative n";
+    if (!xy) return "null xy";
+    if (!height_out) return "null height_out";
+    return nullptr;
+}
+static void launch_heightfield_sample(int32_t n, const HfField& field, const double* xy, const double* origin, double* height_out, hipStream_t s) {
+    HfSampleArgs a;
+    a.f = field; a.n = n; a.xy = xy; a.origin = origin; a.out = height_out;
+    hipLaunchKernelGGL(a1mpc_heightfield_sample_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(n) + 63) / 64)), dim3(64), 0, s, a);
+}
+a1mpc_status a1mpc_heightfield_sample_batch_device(a1mpc_handle h, const a1mpc_heightfield* field, int32_t n, const double* d_xy, const double* d_origin,
+                                                   double* d_height_out, void* hip_stream) {
+    if (const char* bad = invalid_heightfield_sample(h, field, n, d_xy, d_height_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    A1_STAGE_DEVICE(hip_stream);
+    A1_STAGE_LAUNCH(launch_heightfield_sample(n, make_hf_field(*field, field->height), d_xy, d_origin, d_height_out, s));
+    return A1MPC_OK;
+}
+a1mpc_status a1mpc_heightfield_sample_batch(a1mpc_handle h, const a1mpc_heightfield* field, int32_t n, const double* xy, const double* origin, double* height_out) {
+    if (const char* bad = invalid_heightfield_sample(h, field, n, xy, height_out)) return fail(A1MPC_ERR_INVALID_ARGUMENT, bad);
+    if (const char* big = too_large_to_stage(*field)) return fail(A1MPC_ERR_BATCH_TOO_LARGE, big);
+    A1_STAGE_DEVICE(nullptr);
+    Staging sg(h, n, s);
+    HfStaged hf;
+    const double *d_xy = sg.in(xy, 2), *d_or = origin ? sg.in(origin, 3) : nullptr;
+    double* d_out = sg.out(height_out, 1);
+    A1_STAGED(sg);
+    if (a1mpc_status st = hf.fill(*field, s); st != A1MPC_OK) return st;
+    A1_STAGE_LAUNCH(launch_heightfield_sample(n, make_hf_field(*field, hf.d), d_xy, d_or, d_out, s));
     return sg.finish();
 }
 // ---- sensor noise and IMU bias behind the C ABI: a1mpc_sensor_noise_kernel, no handle state

@@ -74,6 +74,11 @@ class WalkConfig(C.Structure):  # a1mpc_walk_config: the plant's configuration, 
     _fields_ = [("plant", PlantConfig), ("swing_track", C.c_double), ("flat_ground", C.c_int32), ("ground_z", C.c_double)]
 
 
+class Heightfield(C.Structure):  # a1mpc_heightfield: a gridded field of heights under the walking plant; `height` is a device pointer in the _device entries
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("x0", C.c_double), ("y0", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("interp", C.c_int32),
+                ("height", C.c_void_p)]
+
+
 class NoiseConfig(C.Structure):  # a1mpc_noise_config: the generator's seed and the levels of the eight noise channels (0 = that channel is off)
     _fields_ = [("seed", C.c_uint64), ("gyro_sigma", C.c_double), ("acc_sigma", C.c_double), ("gyro_bias_walk", C.c_double), ("acc_bias_walk", C.c_double),
                 ("att_sigma", C.c_double), ("joint_pos_sigma", C.c_double), ("joint_vel_sigma", C.c_double), ("foot_force_sigma", C.c_double)]
@@ -121,7 +126,8 @@ class TickBuffers(C.Structure):  # a1mpc_tick_buffers: device pointers, in the h
     _fields_ = [(k, C.c_void_p) for k in TICK_BUFFER_FIELDS]
 
 
-EXPORTS = ["a1mpc_default_respawn_config", "a1mpc_respawn_reset_batch", "a1mpc_respawn_reset_batch_device", "a1mpc_respawn_batch", "a1mpc_respawn_batch_device",
+EXPORTS = ["a1mpc_default_heightfield", "a1mpc_heightfield_step_batch", "a1mpc_heightfield_step_batch_device", "a1mpc_heightfield_sample_batch",
+           "a1mpc_heightfield_sample_batch_device", "a1mpc_default_respawn_config", "a1mpc_respawn_reset_batch", "a1mpc_respawn_reset_batch_device", "a1mpc_respawn_batch", "a1mpc_respawn_batch_device",
            "a1mpc_respawn_rows_device", "a1mpc_default_episode_config", "a1mpc_episode_update_batch", "a1mpc_episode_update_batch_device", "a1mpc_episode_summary_batch",
            "a1mpc_episode_summary_batch_device", "a1mpc_default_noise_config", "a1mpc_sensor_noise_batch", "a1mpc_sensor_noise_batch_device",
            "a1mpc_ground_step_batch", "a1mpc_ground_step_batch_device", "a1mpc_touch_sensors_batch", "a1mpc_touch_sensors_batch_device",
@@ -275,6 +281,15 @@ def load_library(path=None):
         lib.a1mpc_touch_sensors_batch.restype = C.c_int
         lib.a1mpc_touch_sensors_batch_device.argtypes = [vp, i32, vpp, i32] + [vpp] * 7 + [C.c_double, dp, dp] + [vpp] * 9 + [vpp]
         lib.a1mpc_touch_sensors_batch_device.restype = C.c_int
+    if path == _build.LIB_PATH or hasattr(lib, "a1mpc_heightfield_step_batch"):   # (height-field terrain; an older build bound by hand for an A/B lacks it)
+        hfp = C.POINTER(Heightfield)
+        lib.a1mpc_default_heightfield.argtypes = [hfp]; lib.a1mpc_default_heightfield.restype = None
+        lib.a1mpc_heightfield_step_batch.argtypes = [vp, C.POINTER(WalkConfig), i32, dp, i32, dp, dp, dp, u8p, dp, dp, dp, hfp, dp, dp, dp, dp, dp, u8p, dp]
+        lib.a1mpc_heightfield_step_batch.restype = C.c_int
+        lib.a1mpc_heightfield_step_batch_device.argtypes = [vp, C.POINTER(WalkConfig), i32, vpp, i32] + [vpp] * 7 + [hfp] + [vpp] * 7 + [vpp]
+        lib.a1mpc_heightfield_step_batch_device.restype = C.c_int
+        lib.a1mpc_heightfield_sample_batch.argtypes = [vp, hfp, i32, dp, dp, dp]; lib.a1mpc_heightfield_sample_batch.restype = C.c_int
+        lib.a1mpc_heightfield_sample_batch_device.argtypes = [vp, hfp, i32, vpp, vpp, vpp, vpp]; lib.a1mpc_heightfield_sample_batch_device.restype = C.c_int
     if path == _build.LIB_PATH or hasattr(lib, "a1mpc_sensor_noise_batch"):   # (sensor noise and IMU bias; an older build bound by hand for an A/B lacks them)
         u64 = C.c_uint64
         lib.a1mpc_default_noise_config.argtypes = [C.POINTER(NoiseConfig)]; lib.a1mpc_default_noise_config.restype = None
@@ -377,6 +392,24 @@ def _dev(t):
 def _f64(a, shape):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a.reshape(shape)
+
+
+class HeightfieldOnDevice:
+    """What Engine.heightfield returns: heights (ny, nx) on the engine's device with the a1mpc_heightfield that points at them.  .struct is what the _device entries
+    take, .host the same descriptor over the host copy for the host-pointer entries; .tensor and .heights keep both alive as long as the object lives"""
+
+    def __init__(self, engine, heights, x0=0.0, y0=0.0, dx=1.0, dy=1.0, interp=0):
+        import torch
+        h = np.ascontiguousarray(heights, dtype=np.float64)
+        if h.ndim != 2:
+            raise ValueError("heights must be (ny, nx)")
+        self.heights = h
+        self.ny, self.nx = h.shape
+        self.tensor = torch.from_numpy(h if h.flags.writeable else h.copy()).to(f"cuda:{engine.device}")   # (torch does not take a read-only array)
+        self.struct, self.host = Heightfield(), Heightfield()
+        for s, ptr in ((self.struct, self.tensor.data_ptr()), (self.host, h.ctypes.data)):
+            engine.lib.a1mpc_default_heightfield(C.byref(s))
+            s.nx, s.ny, s.x0, s.y0, s.dx, s.dy, s.interp, s.height = self.nx, self.ny, float(x0), float(y0), float(dx), float(dy), int(interp), ptr
 
 
 class Engine:
@@ -775,6 +808,67 @@ class Engine:
                                                             _dev(d_imu_acc_raw), _dev(d_imu_gyro_raw), _dev(d_joint_pos), _dev(d_joint_vel), _dev(d_foot_force), _dev(d_reach),
                                                             _dev(d_foot_pos_rel), _dev(d_foot_vel_rel), C.c_void_p(int(stream)) if stream else None)
         _check(self.lib, rc, "a1mpc_touch_sensors_batch_device")
+
+    # ---- height-field terrain: one gridded field of heights under the walk step (stairs, rough ground), reached by every robot through an optional origin row ----
+    def heightfield(self, heights, x0=0.0, y0=0.0, dx=1.0, dy=1.0, interp=0):
+        """a HeightfieldOnDevice of heights (ny, nx): the heights as a device tensor and the a1mpc_heightfield that points at it, both kept alive by the object.  Its
+        .host is the same descriptor over the host copy, for the host-pointer entries"""
+        return HeightfieldOnDevice(self, heights, x0, y0, dx, dy, interp)
+
+    @staticmethod
+    def _field(field, device):
+        if isinstance(field, HeightfieldOnDevice):
+            return field.struct if device else field.host
+        return field   # an engine.Heightfield filled by the caller
+
+    def walk_step_heightfield(self, state, R, foot, grf, contacts, R_z=None, foot_target=None, field=None, origin=None, ext_wrench=None, walk=None, ground_out=True):
+        """walk_step_ground's dict and ground (n, 3) = (hf under the body, 0, 0), or None with ground_out False: a1mpc_heightfield_step_batch.  field: what heightfield()
+        returns (or an engine.Heightfield over host memory); origin (n, 3) = (ox, oy, oz) per robot or None"""
+        wc = self.walk_config() if walk is None else walk
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        n, stride = state.shape
+        R = _f64(R, (n, 9)); foot = _f64(foot, (n, 12)); grf = _f64(grf, (n, 12))
+        ct = np.ascontiguousarray(contacts, dtype=np.uint8).reshape(n, 4)
+        ext = None if ext_wrench is None else _f64(ext_wrench, (n, 6)); og = None if origin is None else _f64(origin, (n, 3))
+        Rz = None if R_z is None else _f64(R_z, (n, 9)); tg = None if foot_target is None else _f64(foot_target, (n, 12))
+        state_out = state.copy(); R_out = np.zeros((n, 9)); foot_out = np.zeros((n, 12)); vel_out = np.zeros((n, 12)); touch = np.zeros((n, 4), np.uint8)
+        gout = np.zeros((n, 3)) if ground_out else None
+        f = self._field(field, False)
+        rc = self.lib.a1mpc_heightfield_step_batch(self._h, C.byref(wc), n, _dp(state), int(stride), _dp(R), _dp(foot), _dp(grf), _u8p(ct), _dp(ext), _dp(Rz), _dp(tg),
+                                                   None if f is None else C.byref(f), _dp(og), _dp(state_out), _dp(R_out), _dp(foot_out), _dp(vel_out), _u8p(touch),
+                                                   _dp(gout))
+        _check(self.lib, rc, "a1mpc_heightfield_step_batch")
+        return dict(state=state_out, R=R_out, foot=foot_out, foot_vel_body=vel_out, touch=touch, ground=gout)
+
+    def walk_step_heightfield_device(self, n, d_state, state_stride, d_R, d_foot, d_grf, d_contacts, d_R_z, d_foot_target, d_foot_vel_body, d_touch, field=None,
+                                     d_origin=None, d_ext_wrench=None, d_state_out=None, d_R_out=None, d_foot_out=None, walk=None, stream=None, d_ground_out=None):
+        """walk_step_ground_device with field, d_origin (n, 3; optional) where d_ground is, and d_ground_out (n, 3; optional, written) last"""
+        wc = self.walk_config() if walk is None else walk
+        out = lambda o, i: _dev(i if o is None else o)
+        f = self._field(field, True)
+        rc = self.lib.a1mpc_heightfield_step_batch_device(self._h, C.byref(wc), int(n), _dev(d_state), int(state_stride), _dev(d_R), _dev(d_foot), _dev(d_grf),
+                                                          _dev(d_contacts), _dev(d_ext_wrench), _dev(d_R_z), _dev(d_foot_target), None if f is None else C.byref(f),
+                                                          _dev(d_origin), out(d_state_out, d_state), out(d_R_out, d_R), out(d_foot_out, d_foot), _dev(d_foot_vel_body),
+                                                          _dev(d_touch), _dev(d_ground_out), C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_heightfield_step_batch_device")
+
+    def heightfield_sample(self, field, xy, origin=None):
+        """hf at xy (n, 2), with origin (n, 3) or None -> (n,) heights: a1mpc_heightfield_sample_batch"""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = xy.shape[0]
+        og = None if origin is None else _f64(origin, (n, 3))
+        out = np.zeros(n)
+        f = self._field(field, False)
+        rc = self.lib.a1mpc_heightfield_sample_batch(self._h, None if f is None else C.byref(f), n, _dp(xy), _dp(og), _dp(out))
+        _check(self.lib, rc, "a1mpc_heightfield_sample_batch")
+        return out
+
+    def heightfield_sample_device(self, field, n, d_xy, d_height_out, d_origin=None, stream=None):
+        """device pointers, asynchronous on `stream`: d_xy (n, 2), d_origin (n, 3; optional), d_height_out (n), written"""
+        f = self._field(field, True)
+        rc = self.lib.a1mpc_heightfield_sample_batch_device(self._h, None if f is None else C.byref(f), int(n), _dev(d_xy), _dev(d_origin), _dev(d_height_out),
+                                                            C.c_void_p(int(stream)) if stream else None)
+        _check(self.lib, rc, "a1mpc_heightfield_sample_batch_device")
 
     # ---- sensor noise and IMU bias: counter-based Gaussian noise on the synthesised sensors, in place, the same bits for a robot and tick in every batch ----
     def noise_config(self, **fields):

@@ -909,6 +909,82 @@ a1mpc_status a1mpc_touch_sensors_batch_device(a1mpc_handle h, int32_t n, const d
                                                    void* hip_stream);
 
 /*
+ * Height-field terrain for the walking plant: ONE gridded field of heights under a1mpc_walk_step_batch in place of a1mpc_ground_step_batch's plane per robot -- stairs,
+ * kerbs, rough ground.  With it  a1mpc_touch_sensors_batch_device -> a1mpc_control_tick_sensors_device -> a1mpc_heightfield_step_batch_device  runs on one stream
+ * with no host copy; the step's touch bytes feed the touch sensors, its ground_out rows feed a1mpc_episode_update_batch, and a1mpc_heightfield_sample_batch places
+ * spawn templates on the terrain in front of a1mpc_respawn_rows_device.  Kernels of their own (a1mpc_walk_step_heightfield_kernel, a1mpc_heightfield_sample_kernel):
+ * every entry above is unchanged, and these five symbols are a family of their own, a1mpc_*heightfield*.  The handle gets no state.
+ *
+ * The field.  height is ny x nx doubles, row-major, x fastest: H[j * nx + i] is the height of node (i, j) at the world position (x0 + i dx, y0 + j dy).  It is a DEVICE
+ * pointer in the _device entries and a host pointer in the host entries; the struct itself is always host memory, read during the call.
+ *
+ * The sampling rule hf(X, Y), one IEEE operation per step in exactly this order, no FMA:
+ *   inv_dx = 1.0 / dx, inv_dy = 1.0 / dy          once on the host, passed to the kernels by value
+ *   with a per-robot origin row (ox, oy, oz):     ux = ((X - ox) - x0) * inv_dx,   uy = ((Y - oy) - y0) * inv_dy
+ *   with origin NULL:                             ux = (X - x0) * inv_dx,          uy = (Y - y0) * inv_dy        (the subtraction is skipped, not done with 0)
+ *   valid = (ux == ux) && (uy == uy)
+ *   cx = ux > 0.0 ? ux : 0.0;  cx = cx < (double)(nx - 1) ? cx : (double)(nx - 1);   cy likewise with ny    (a NaN goes to 0: the index is always in range)
+ *        only cx and cy are ever converted to an integer; they are finite and lie in [0, nx - 1] and [0, ny - 1]
+ *   interp == 0 (cell-constant: steps):  i = (int)cx, j = (int)cy, h = H[j * nx + i].  Cell (i, j) spans [x0 + i dx, x0 + (i + 1) dx) x [y0 + j dy, y0 + (j + 1) dy);
+ *        the last node of an axis owns only its own line
+ *   interp == 1 (bilinear):  i = (int)cx; i = i < nx - 1 ? i : nx - 2;  tx = cx - (double)i;  j and ty likewise;
+ *        h00 = H[j * nx + i], h10 = H[j * nx + i + 1], h01 = H[(j + 1) * nx + i], h11 = H[(j + 1) * nx + i + 1];
+ *        a = h00 + tx * (h10 - h00);  b = h01 + tx * (h11 - h01);  h = a + ty * (b - a)
+ *   top = valid ? h : NaN, selected;  with origin given, top = top + oz;  hf(X, Y) = top
+ * Outside the grid the field continues with its edge values (+-inf is clamped like any other value and gives a finite height); a NaN coordinate gives a NaN height.
+ * The index arithmetic is 64-bit.  Several terrains in one batch are tiles of one field: robot b's origin row moves the field's frame to (ox, oy) and lifts it by oz.
+ *
+ * a1mpc_heightfield_step_batch is a1mpc_ground_step_batch with (field, origin) in place of ground and one more optional output, ground_out, after touch_out:
+ *   in   field        the descriptor above
+ *        origin       n x 3, optional: (ox, oy, oz) of robot b
+ *   after the last sub-step, for every leg:  X = pos'_x + r'_x,  Y = pos'_y + r'_y,  gz = hf(X, Y) - pos'_z;  then the ground step's rule unchanged: a stance foot gets
+ *        r'_z = gz;  a swing foot gets r'_z = (r'_z < gz) ? gz : r'_z;  touch_out (n x 4 bytes, required) is 1 for a stance leg, and for a swing leg 1 exactly when
+ *        that comparison lifted the foot (a NaN keeps the foot and gives 0).  The projection is VERTICAL.  cfg->flat_ground and cfg->ground_z are not read
+ *   out  ground_out   n x 3, optional: (hf(pos'_x, pos'_y), +0, +0) -- the row a1mpc_episode_update_batch takes as `ground`: its hz = (z0 + sx X) + sy Y is then the
+ *                     terrain height under the body, bit for bit for a finite position; it is also the height condition of the closed loops
+ * Reductions: with a constant field of a finite value c (either interp) and origin NULL every other output is a1mpc_ground_step_batch's with ground = (c, 0, 0), bit for
+ * bit on finite inputs.  A robot's outputs do not depend on its position in the batch, on the batch size, or on the other robots.
+ * In-place use of state, R_world and foot_abs follows a1mpc_ground_step_batch's rule.  n == 0 is A1MPC_OK and launches nothing.
+ *
+ * a1mpc_heightfield_sample_batch is the rule on its own, one point per lane: xy n x 2 (X, Y), origin n x 3 optional, height_out n.
+ *
+ * Refused with A1MPC_ERR_INVALID_ARGUMENT (a1mpc_last_error names the field) before any launch, every array left untouched.  The field is checked FIRST, in front of
+ * the handle, so whether or not a GPU is present: a null descriptor or a null height; interp other than 0 or 1; nx or ny below 1 with interp == 0 or below 2 with
+ * interp == 1; nx or ny above 32768; dx or dy not finite or not positive; x0 or y0 not finite; an inv_dx or inv_dy that is not finite.  Then, of the step, everything
+ * a1mpc_ground_step_batch refuses (cfg's own plane is never checked); of the sample entry a null handle, n < 0, a null xy or height_out.  The host-pointer entries
+ * stage the WHOLE field on every call, as every host-pointer entry stages its inputs: they are for tests and small fields, and refuse a field of more than 2^20 nodes
+ * with A1MPC_ERR_BATCH_TOO_LARGE (a stated condition, not a measurement).  Their copy of the field is a device allocation that lives for the call (the handle gets no
+ * state): unlike the other host-pointer entries, which use the handle's staging alone, they allocate and free device memory on every call, and the free synchronises the
+ * WHOLE device, so they disturb work on other streams -- keep them out of a loop that shares the device, and use the _device entries there.
+ * n > max_batch is A1MPC_ERR_BATCH_TOO_LARGE.  The _device entries are asynchronous on
+ * hip_stream (NULL = the handle's); the field's heights must stay valid until the stream has passed the call.
+ *
+ * What it is not: the projection is vertical, so a swing foot that meets a riser is lifted onto the tread and reports a touch, not a collision; there is no slip and no
+ * friction cone; nothing stops the BODY itself at the field; there is ONE field per call -- several terrains in one batch are tiles of one field, reached through
+ * origin; and the tick's foot preview still plans flat-ground footholds.
+ */
+typedef struct a1mpc_heightfield {
+    int32_t nx, ny;         /* nodes along world x / y */
+    double x0, y0;          /* world position of node (0, 0) */
+    double dx, dy;          /* node spacing, > 0 */
+    int32_t interp;         /* 0: cell-constant (steps), 1: bilinear */
+    const double* height;   /* ny x nx, row-major, x fastest: H[j * nx + i]; a DEVICE pointer in the _device entries, a host pointer in the host entries */
+} a1mpc_heightfield;
+void a1mpc_default_heightfield(a1mpc_heightfield* field);   /* 0, 0, 0.0, 0.0, 1.0, 1.0, 0, NULL */
+a1mpc_status a1mpc_heightfield_step_batch(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* state_in, int32_t state_stride, const double* R_world,
+                                          const double* foot_abs, const double* grf_body, const uint8_t* contacts, const double* ext_wrench, const double* R_z,
+                                          const double* foot_target, const a1mpc_heightfield* field, const double* origin, double* state_out, double* R_world_out,
+                                          double* foot_abs_out, double* foot_vel_body_out, uint8_t* touch_out, double* ground_out);
+a1mpc_status a1mpc_heightfield_step_batch_device(a1mpc_handle h, const a1mpc_walk_config* cfg, int32_t n, const double* d_state_in, int32_t state_stride,
+                                                 const double* d_R_world, const double* d_foot_abs, const double* d_grf_body, const uint8_t* d_contacts,
+                                                 const double* d_ext_wrench, const double* d_R_z, const double* d_foot_target, const a1mpc_heightfield* field,
+                                                 const double* d_origin, double* d_state_out, double* d_R_world_out, double* d_foot_abs_out, double* d_foot_vel_body_out,
+                                                 uint8_t* d_touch_out, double* d_ground_out, void* hip_stream);
+a1mpc_status a1mpc_heightfield_sample_batch(a1mpc_handle h, const a1mpc_heightfield* field, int32_t n, const double* xy, const double* origin, double* height_out);
+a1mpc_status a1mpc_heightfield_sample_batch_device(a1mpc_handle h, const a1mpc_heightfield* field, int32_t n, const double* d_xy, const double* d_origin,
+                                                   double* d_height_out, void* hip_stream);
+
+/*
  * Sensor noise and IMU bias on the device, reproducible per robot and tick: white Gaussian noise on the six sensor arrays that a1mpc_sensor_synthesis_batch,
  * a1mpc_walk_sensors_batch and a1mpc_touch_sensors_batch write, and a random-walk bias on the IMU.  With it  a1mpc_walk_sensors_batch_device ->
  * a1mpc_sensor_noise_batch_device -> a1mpc_control_tick_sensors_device -> a1mpc_walk_step_batch_device  runs on one stream with no host copy, and the EKF's
